@@ -28,6 +28,22 @@ ways (--shard), total work fixed either way ("strong" scaling):
   (ptCommGatherSampleBuffer) is inside the step.
 
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline figure needs and no more: set-up, the
+warm-up frames, the timed frames, --dump-outputs, the line.  --full adds
+every secondary measurement, each outside the headline's own work: kernel
+timing by HIP events inside the timed frames (every --profile-period-th
+round) and the roofline / limiter fields computed from it, the steady-state
+rounds, the traversal counters of one extra extend, and the CPU baseline.
+
+--dump-outputs DIR writes what the last timed frame produced on rank 0, as a
+caller of the frame would receive it: DIR/sample_buffer.npy (the rgba32f
+accumulator, (H, W, 4) float32: CIE XYZ sums + sample count; for N GPUs the
+reduced or gathered one) and DIR/frame_counts.npy (float64: the frame's
+rounds and completed samples).  An accumulator over DUMP_MAX_BYTES is written
+as a fixed, seeded sample of its pixels ((K, 4), rows in ascending pixel
+index).  Scene, seeds and schedule are functions of the arguments alone, so
+two runs with the same arguments dump the same arrays.
 """
 from __future__ import annotations
 
@@ -60,6 +76,8 @@ PATH_BYTES_PER_RAY = 220  # SURVEY.md §8(d) whole-path definition
 STEADY_ROUNDS = 64        # secondary key: steady-state rounds timed after the frames
 FILL_SLOTS = 1 << 21      # slots per launch a band partition is filled to with path streams (C3 frame: 2.07 M)
 SETTLE_ROUNDS = 32        # ... after this many rounds past a restart
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: a larger accumulator is sampled down to this
+DUMP_SEED = 20240607       # ... with this seed
 
 
 def load_package():
@@ -277,6 +295,21 @@ def cpu_baseline(pt, scene, width, height, config, settle_rounds=CPU_SETTLE_ROUN
     }
 
 
+def dump_outputs(path, accum, rounds, samples):
+    """--dump-outputs: the last timed frame as its caller receives it (the
+    module docstring names the files).  `accum` is the (H, W, 4) float32
+    accumulator read back from the device."""
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    a = np.ascontiguousarray(accum, dtype=np.float32)
+    if a.nbytes > DUMP_MAX_BYTES:
+        px = a.reshape(-1, 4)
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(px.shape[0], DUMP_MAX_BYTES // 16, replace=False))
+        a = np.ascontiguousarray(px[keep])
+    np.save(out / "sample_buffer.npy", a)
+    np.save(out / "frame_counts.npy", np.array([rounds, samples], dtype=np.float64))
+
+
 def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -326,8 +359,14 @@ def main():
     ap.add_argument("--spp", type=int, default=0, help="frame spp target (default: the config's)")
     ap.add_argument("--profile-period", type=int, default=8,
                     help="time the kernels of every N-th round (HIP events) inside the timed frames")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-steady", action="store_true", help="skip the steady-state secondary measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="add the secondary measurements: kernel timing + roofline / limiter, steady state, "
+                         "traversal counters, CPU baseline (off: the headline figure alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-steady", action="store_true",
+                    help="with --full: skip the steady-state secondary measurement")
     ap.add_argument("--one-gpu-flow-check", action="store_true",
                     help="every rank on device 0 (multi-rank flow check on a one-GPU box; timings not meaningful)")
     ap.add_argument("--launch-check", action="store_true",
@@ -344,6 +383,8 @@ def main():
                     help="multi-GPU split: samples (whole frame per rank, own RNG stream) or 16-row pixel bands; "
                          "auto = bands for C4 (pixel-tiled by its config), samples otherwise")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # N ranks: launch them first (before anything touches the GPU), or check
     # the launcher's world size against --gpus.
@@ -485,8 +526,10 @@ def main():
     # Kernel durations: HIP events around the extend / shade launches of every
     # profile_period-th round of the timed frames (an event pair per launch
     # costs issue time; sampling keeps the measured loop representative).
-    dev.set_profiling(True, period=args.profile_period)
-    dev.reset_kernel_stats()
+    # --full only: the headline figure does not need them.
+    if args.full:
+        dev.set_profiling(True, period=args.profile_period)
+        dev.reset_kernel_stats()
     barrier()
     dev.synchronize()
     t0 = time.perf_counter()
@@ -497,18 +540,25 @@ def main():
     dt = time.perf_counter() - t0
     # Per kernel: timed launches, rounds they covered (a round batch covers
     # several) and their total time.
-    kstats = {k: (*dev.kernel_stats(i), dev.kernel_rounds(i)) for k, i in KERNEL_IDS.items()}
-    dev.set_profiling(False)
+    kstats = {}
+    if args.full:
+        kstats = {k: (*dev.kernel_stats(i), dev.kernel_rounds(i)) for k, i in KERNEL_IDS.items()}
+        dev.set_profiling(False)
 
     rounds_local = sum(f[0] for f in frames)
     samples_local = sum(f[1] for f in frames)
     rays_local = rounds_local * slots_owned
     assert all(f[1] >= target for f in frames), "a frame ended short of its spp target"
 
+    # The last timed frame as rank 0 holds it after the frame-end exchange,
+    # before anything below renders into the same buffer again.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, (total if total is not None else sb).read(), *frames[-1])
+
     # Secondary: the steady-state rate (rounds after the path population
     # settled, no Reset in the window), outside the timed frames.
     steady = None
-    if not args.no_steady:
+    if args.full and not args.no_steady:
         r.reset()
         r.run(2)
         r.run_rounds(SETTLE_ROUNDS)     # consecutive Run(1) rounds, as the frames run them
@@ -523,7 +573,7 @@ def main():
 
     # Traversal counters of one extra extend over the current rays (outside
     # the timed region; the next Run overwrites the same hit records).
-    trav = r.extend_stats()
+    trav = r.extend_stats() if args.full else None
     if dist is not None:
         import torch
         t = torch.tensor([dt], dtype=torch.float64)
@@ -551,53 +601,6 @@ def main():
         return
 
     mrays = rays / dt / 1e6
-    kernels = {}
-    for name, (n_k, ms_k, rounds_k) in kstats.items():
-        if n_k:
-            avg = ms_k / max(rounds_k, 1)   # per round (= per launch except for round batches)
-            kernels[name] = {"avg_ms": avg, "gbps": ALG_BYTES[name] * launch_slots / (avg * 1e-3) / 1e9,
-                             "launches": n_k, "rounds": rounds_k}
-    # traversal-level cache rate below: extend's time per round, or the fused kernels'
-    avg_ext = next(kernels[k]["avg_ms"] for k in ("extend", "round", "rounds") if k in kernels)
-    # The dominant kernel: the most device time over the timed rounds (C1's
-    # frames are mostly round batches, with two single fused rounds each).
-    dom = max(kernels, key=lambda k: kernels[k]["avg_ms"] * kernels[k]["rounds"])
-    achieved = kernels[dom]["gbps"]
-    wall_round_ms = dt / max(rounds_local, 1) * 1e3
-    ksum = {k: v["avg_ms"] * (split["groups"] if k in ("extend", "shade") else 1) for k, v in kernels.items()
-            if k in ("extend", "shade", "round", "rounds")}
-    share_ms = wall_round_ms * ksum[dom] / max(sum(ksum.values()), 1e-12) if dom in ksum else None
-    apportioned = ({"ms_per_round": round(share_ms, 4), "wall_ms_per_round": round(wall_round_ms, 4),
-                    "achieved": round(ALG_BYTES[dom] * slots_owned / (share_ms * 1e-3) / 1e9, 2),
-                    "frac": round(ALG_BYTES[dom] * slots_owned / (share_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5)}
-                   if share_ms else None)
-    # The committed PMC profile of this workload: the whole frame's launches
-    # (N = 1 and sample shards), or rank 0's band partition with its path
-    # streams (a launch over other slots than the whole frame's).
-    pkey = str(args.config) if part_n == 1 else f"{args.config}:bands{part_n}x{streams}"
-    prof = profile_for(pkey) or {}
-    kprof = prof.get("kernels", {}).get(dom, {})
-    traffic = kprof.get("hbm_bytes")
-    # The roofline that binds the dominant kernel (VERDICT r04 #7, r05 #2),
-    # from the committed PMC of this workload, every figure in ONE machine
-    # state -- the profiled dispatches, which rocprofv3 serialises:
-    #   issue_frac   = VALU issue fraction x active lanes / 64 (the chip's
-    #                  lane-issue capacity doing useful work),
-    #   traffic_frac = the dispatches' HBM bytes / their own duration / peak.
-    # Whichever resource is closer to its peak in that state binds; `bound`
-    # says which, and the line's frac stays priced against HBM.
-    dissue = (prof.get("issue") or {}).get(dom) or {}
-    issue_frac = (round(dissue["valu_issue_frac"] * dissue["valu_active_lanes"] / 64.0, 4)
-                  if "valu_issue_frac" in dissue and "valu_active_lanes" in dissue else None)
-    dispatch_ms = kprof.get("dispatch_ms")
-    traffic_frac = (round(traffic / (dispatch_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
-                    if traffic is not None and dispatch_ms else None)
-    if "valu_issue_frac" not in dissue or traffic_frac is None:
-        binding = None
-    elif dissue["valu_issue_frac"] > traffic_frac:
-        binding = "valu_issue"
-    else:
-        binding = "hbm"
     # Which image property the N-GPU frame keeps (VERDICT r04 #7 / ADVICE r04):
     # band partitions with one path stream are the one-GPU frame bit for bit;
     # sample shards and band path streams add independent RNG streams
@@ -663,59 +666,112 @@ def main():
             "rays": int(rays),
             "samples": int(samples),
         },
-        "steady_state": steady,
-        "roofline": {
-            # The limiter of the dominant kernel in its profiled state (HBM
-            # or VALU issue); peak / frac are the HBM roofline either way.
-            "bound": binding or "hbm",
-            "priced_against": "hbm",
-            "kernel": dom,
-            # The dominant kernel's share of the chip: the frame's wall time
-            # per round apportioned among the kernels by their summed launch
-            # time per round (tile groups run K launches of each kernel
-            # concurrently), its algorithmic bytes per round over that share.
-            # Kernel time <= step time by construction.
-            "achieved": apportioned["achieved"] if apportioned else round(achieved, 2),
-            "peak": HBM_PEAK_GBPS,
-            "unit": "GB/s",
-            "frac": apportioned["frac"] if apportioned else round(achieved / HBM_PEAK_GBPS, 5),
-            "frac_basis": "apportioned chip share per round" if apportioned else "per launch",
-            "traffic": traffic,
-            "traffic_unit": "bytes per launch (HBM, PMC)",
-            "traffic_source": prof.get("profile") if traffic is not None else None,
-            "alg_bytes_per_launch": round(ALG_BYTES[dom] * launch_slots),
-            "alg_bytes_per_round": round(ALG_BYTES[dom] * slots_owned),
-            "split_groups": split["groups"],
-            "slots_per_timed_launch": round(launch_slots),
-            "apportioned": apportioned,
-            # One timed launch's own rate: its bytes over its own duration.
-            # With tile groups, `split_groups` such launches overlap, so this
-            # is not a share of the chip (secondary).
-            "per_launch": {"avg_ms": round(kernels[dom]["avg_ms"], 4), "achieved": round(achieved, 2),
-                           "frac": round(achieved / HBM_PEAK_GBPS, 5)},
-            "alg_bytes_per_slot": ALG_BYTES[dom],
-            "launch_avg_ms": {k: round(v["avg_ms"], 4) for k, v in kernels.items()},
-            "launches_timed": {**{k: v[0] for k, v in kstats.items()}, "every_nth_round": args.profile_period},
-            "rounds_timed": {k: v[2] for k, v in kstats.items()},
-            "path_gbps_220B_per_ray": round(PATH_BYTES_PER_RAY * rays / dt / 1e9, 2),
-            # BASELINE.md's whole-path definition: 220 B per ray over the frame time.
-            "path_frac": round(PATH_BYTES_PER_RAY * rays / dt / 1e9 / HBM_PEAK_GBPS, 5),
-            # Both from the committed PMC's serialised dispatches (above).
-            "traffic_frac": traffic_frac,
-            "issue_frac": issue_frac,
-            "pmc_state": "serialised profiled dispatches (rocprofv3 --pmc): counters and durations of the same dispatches",
-            "pmc_dispatch_ms": dispatch_ms,
-            "binding": binding,
-        },
-        # What bounds the dominant kernel instead of HBM (PMC of this config's
-        # committed profile): fraction of the chip's VALU issue slots used and
-        # active lanes per VALU instruction (of 64; divergence).  null when no
-        # profile of this config is committed.
-        "limiter": ({"kind": "valu_issue", "kernel": dom, **(prof.get("issue", {}).get(dom) or {}),
-                     "per_kernel": {k: prof.get("issue", {}).get(k) for k in ("extend", "shade", "round", "rounds")
-                                    if prof.get("issue", {}).get(k)},
-                     "source": prof.get("profile"), "profile_key": pkey} if prof else None),
     }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        shutdown()
+        return
+
+    # --full: the secondary measurements' fields.
+    kernels = {}
+    for name, (n_k, ms_k, rounds_k) in kstats.items():
+        if n_k:
+            avg = ms_k / max(rounds_k, 1)   # per round (= per launch except for round batches)
+            kernels[name] = {"avg_ms": avg, "gbps": ALG_BYTES[name] * launch_slots / (avg * 1e-3) / 1e9,
+                             "launches": n_k, "rounds": rounds_k}
+    # traversal-level cache rate below: extend's time per round, or the fused kernels'
+    avg_ext = next(kernels[k]["avg_ms"] for k in ("extend", "round", "rounds") if k in kernels)
+    # The dominant kernel: the most device time over the timed rounds (C1's
+    # frames are mostly round batches, with two single fused rounds each).
+    dom = max(kernels, key=lambda k: kernels[k]["avg_ms"] * kernels[k]["rounds"])
+    achieved = kernels[dom]["gbps"]
+    wall_round_ms = dt / max(rounds_local, 1) * 1e3
+    ksum = {k: v["avg_ms"] * (split["groups"] if k in ("extend", "shade") else 1) for k, v in kernels.items()
+            if k in ("extend", "shade", "round", "rounds")}
+    share_ms = wall_round_ms * ksum[dom] / max(sum(ksum.values()), 1e-12) if dom in ksum else None
+    apportioned = ({"ms_per_round": round(share_ms, 4), "wall_ms_per_round": round(wall_round_ms, 4),
+                    "achieved": round(ALG_BYTES[dom] * slots_owned / (share_ms * 1e-3) / 1e9, 2),
+                    "frac": round(ALG_BYTES[dom] * slots_owned / (share_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 5)}
+                   if share_ms else None)
+    # The committed PMC profile of this workload: the whole frame's launches
+    # (N = 1 and sample shards), or rank 0's band partition with its path
+    # streams (a launch over other slots than the whole frame's).
+    pkey = str(args.config) if part_n == 1 else f"{args.config}:bands{part_n}x{streams}"
+    prof = profile_for(pkey) or {}
+    kprof = prof.get("kernels", {}).get(dom, {})
+    traffic = kprof.get("hbm_bytes")
+    # The roofline that binds the dominant kernel (VERDICT r04 #7, r05 #2),
+    # from the committed PMC of this workload, every figure in ONE machine
+    # state -- the profiled dispatches, which rocprofv3 serialises:
+    #   issue_frac   = VALU issue fraction x active lanes / 64 (the chip's
+    #                  lane-issue capacity doing useful work),
+    #   traffic_frac = the dispatches' HBM bytes / their own duration / peak.
+    # Whichever resource is closer to its peak in that state binds; `bound`
+    # says which, and the line's frac stays priced against HBM.
+    dissue = (prof.get("issue") or {}).get(dom) or {}
+    issue_frac = (round(dissue["valu_issue_frac"] * dissue["valu_active_lanes"] / 64.0, 4)
+                  if "valu_issue_frac" in dissue and "valu_active_lanes" in dissue else None)
+    dispatch_ms = kprof.get("dispatch_ms")
+    traffic_frac = (round(traffic / (dispatch_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4)
+                    if traffic is not None and dispatch_ms else None)
+    if "valu_issue_frac" not in dissue or traffic_frac is None:
+        binding = None
+    elif dissue["valu_issue_frac"] > traffic_frac:
+        binding = "valu_issue"
+    else:
+        binding = "hbm"
+    out["steady_state"] = steady
+    out["roofline"] = {
+        # The limiter of the dominant kernel in its profiled state (HBM
+        # or VALU issue); peak / frac are the HBM roofline either way.
+        "bound": binding or "hbm",
+        "priced_against": "hbm",
+        "kernel": dom,
+        # The dominant kernel's share of the chip: the frame's wall time
+        # per round apportioned among the kernels by their summed launch
+        # time per round (tile groups run K launches of each kernel
+        # concurrently), its algorithmic bytes per round over that share.
+        # Kernel time <= step time by construction.
+        "achieved": apportioned["achieved"] if apportioned else round(achieved, 2),
+        "peak": HBM_PEAK_GBPS,
+        "unit": "GB/s",
+        "frac": apportioned["frac"] if apportioned else round(achieved / HBM_PEAK_GBPS, 5),
+        "frac_basis": "apportioned chip share per round" if apportioned else "per launch",
+        "traffic": traffic,
+        "traffic_unit": "bytes per launch (HBM, PMC)",
+        "traffic_source": prof.get("profile") if traffic is not None else None,
+        "alg_bytes_per_launch": round(ALG_BYTES[dom] * launch_slots),
+        "alg_bytes_per_round": round(ALG_BYTES[dom] * slots_owned),
+        "split_groups": split["groups"],
+        "slots_per_timed_launch": round(launch_slots),
+        "apportioned": apportioned,
+        # One timed launch's own rate: its bytes over its own duration.
+        # With tile groups, `split_groups` such launches overlap, so this
+        # is not a share of the chip (secondary).
+        "per_launch": {"avg_ms": round(kernels[dom]["avg_ms"], 4), "achieved": round(achieved, 2),
+                       "frac": round(achieved / HBM_PEAK_GBPS, 5)},
+        "alg_bytes_per_slot": ALG_BYTES[dom],
+        "launch_avg_ms": {k: round(v["avg_ms"], 4) for k, v in kernels.items()},
+        "launches_timed": {**{k: v[0] for k, v in kstats.items()}, "every_nth_round": args.profile_period},
+        "rounds_timed": {k: v[2] for k, v in kstats.items()},
+        "path_gbps_220B_per_ray": round(PATH_BYTES_PER_RAY * rays / dt / 1e9, 2),
+        # BASELINE.md's whole-path definition: 220 B per ray over the frame time.
+        "path_frac": round(PATH_BYTES_PER_RAY * rays / dt / 1e9 / HBM_PEAK_GBPS, 5),
+        # Both from the committed PMC's serialised dispatches (above).
+        "traffic_frac": traffic_frac,
+        "issue_frac": issue_frac,
+        "pmc_state": "serialised profiled dispatches (rocprofv3 --pmc): counters and durations of the same dispatches",
+        "pmc_dispatch_ms": dispatch_ms,
+        "binding": binding,
+    }
+    # What bounds the dominant kernel instead of HBM (PMC of this config's
+    # committed profile): fraction of the chip's VALU issue slots used and
+    # active lanes per VALU instruction (of 64; divergence).  null when no
+    # profile of this config is committed.
+    out["limiter"] = ({"kind": "valu_issue", "kernel": dom, **(prof.get("issue", {}).get(dom) or {}),
+                       "per_kernel": {k: prof.get("issue", {}).get(k) for k in ("extend", "shade", "round", "rounds")
+                                      if prof.get("issue", {}).get(k)},
+                       "source": prof.get("profile"), "profile_key": pkey} if prof else None)
     # Node/face bytes the traversal pulls through L1/L2 per ray (BVH + faces
     # are cache-resident): internal node = both child boxes (64 B), face 48 B,
     # stack pop = 2 index words (8 B).

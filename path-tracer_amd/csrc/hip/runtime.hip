@@ -893,7 +893,11 @@ pt_sample_buffer* ptCreateSampleBuffer(pt_device* d, uint32_t w, uint32_t h)
     b->width = w;
     b->height = h;
     size_t bytes = (size_t)w * h * sizeof(float4);
-    if (hipMalloc(&b->accum, bytes) != hipSuccess || hipMemset(b->accum, 0, bytes) != hipSuccess) {
+    // Cleared on the device's own stream and waited for: that stream is
+    // non-blocking, so a clear on the null stream is not ordered before the
+    // first ptWriteSampleBuffer and could land after it.
+    if (hipMalloc(&b->accum, bytes) != hipSuccess || hipMemsetAsync(b->accum, 0, bytes, d->stream) != hipSuccess ||
+        hipStreamSynchronize(d->stream) != hipSuccess) {
         SetError("sample buffer allocation failed (%zu bytes)", bytes);
         if (b->accum) (void)hipFree(b->accum);
         delete b;
@@ -1233,8 +1237,10 @@ static int ClassListBuffers(pt_device* d, pt_basic_renderer* r, uint32_t K)
     const size_t nc = (size_t)ptd::PT_OUTCOME_CLASSES * CQ_SUB;
     const uint32_t T = r->slots.tile_count;
     if (!r->cq_counts.ptr) {
+        // Zeroed on the device stream (the tile groups' streams fork from it):
+        // the null stream is not ordered against these non-blocking streams.
         if (r->cq_counts.alloc((PT_MAX_SPLIT + 1) * 2 * nc) != hipSuccess ||
-            hipMemset(r->cq_counts.ptr, 0, (PT_MAX_SPLIT + 1) * 2 * nc * sizeof(uint32_t)) != hipSuccess) {
+            hipMemsetAsync(r->cq_counts.ptr, 0, (PT_MAX_SPLIT + 1) * 2 * nc * sizeof(uint32_t), d->stream) != hipSuccess) {
             SetError("class list allocation failed");
             return -1;
         }
