@@ -26,8 +26,9 @@
  *
  * Additions (no reference counterpart): sample-buffer readback, explicit
  * synchronisation, a bit-exact ray query (ptTraceRays), slot-state readback,
- * per-kernel timing, pixel-band partitioning and an RCCL frame-end reduce for
- * one-process-per-GPU rendering.
+ * per-kernel timing, pixel-band partitioning, an RCCL frame-end reduce for
+ * one-process-per-GPU rendering, and a denoiser (guide images + an
+ * edge-avoiding a-trous filter) in front of ptRenderSampleBuffer.
  *
  * Conventions: creators return NULL on failure and set ptGetLastError();
  * other calls return 0 on success or a non-zero status (HIP / RCCL error
@@ -51,6 +52,7 @@ typedef struct pt_sample_buffer pt_sample_buffer;
 typedef struct pt_basic_renderer pt_basic_renderer;
 typedef struct pt_comm pt_comm;
 typedef struct pt_preview pt_preview;
+typedef struct pt_denoise_guides pt_denoise_guides;
 
 /* Mutable renderer state (src/integrator/basic.hpp:18-25).  The caller writes
  * CameraIndex, RenderFlags, PathLengthLimit and PathTerminationProbability
@@ -98,7 +100,9 @@ enum {
     PT_KERNEL_PREVIEW = 4,
     PT_KERNEL_ROUND   = 5,   /* fused extend + shade of a small partition (one launch per round) */
     PT_KERNEL_ROUNDS  = 6,   /* a round batch: several rounds of every tile in one launch */
-    PT_KERNEL_COUNT   = 7,
+    PT_KERNEL_DENOISE = 7,   /* one a-trous iteration of ptDenoiseSampleBuffer */
+    PT_KERNEL_GUIDES  = 8,   /* ptRenderDenoiseGuides */
+    PT_KERNEL_COUNT   = 9,
 };
 
 /* resolve_parameters (src/integrator/integrator.hpp:12-48). */
@@ -360,6 +364,52 @@ int         ptRetrievePreviewQueryResult(pt_device* device, pt_preview* context,
 /* rgba: RenderSizeX * RenderSizeY * 4 floats (OutColor); aov: one record per pixel. */
 int         ptReadPreviewImage(pt_device* device, pt_preview* context, float* rgba);
 int         ptReadPreviewAOVs(pt_device* device, pt_preview* context, pt_preview_aov* aov);
+
+/* Denoiser (no reference counterpart; definition, kernel design and measured
+ * times in DESIGN.md §6): an edge-avoiding a-trous wavelet filter (Dammertz
+ * et al. 2010) over a sample buffer's mean, steered by guide images -- the
+ * primary hit's normal, distance, base colour and shape -- taken with the
+ * scene's own camera.
+ *
+ * A guides object holds width x height pt_denoise_guide records
+ * (pt_packed.h) and the filter's intermediate image.  ptRenderDenoiseGuides
+ * enqueues one ray per pixel: the central ray of GenerateCameraRay
+ * (scene.glsl.inc:613-655) for packed camera `camera_index` -- sample
+ * position pixel + 0.5, lens point at the lens centre, no random number --
+ * with its velocity packed and unpacked as every ray of the integrator is
+ * between raygen and extend.  normal, time and shape are those of the ray's
+ * pt_hit_record (ptTraceRays); albedo is the preview's BASE_COLOR colour at
+ * Brightness 1 without a selection (the sky's colour on a miss).  An unknown
+ * camera model gives misses with albedo 0.  Fails, launching nothing, on a
+ * NULL handle, a scene of another device or without packs, or
+ * camera_index >= the scene's camera count.  Read blocks; Write replaces the
+ * records (e.g. guides computed elsewhere). */
+pt_denoise_guides* ptCreateDenoiseGuides(pt_device* device, uint32_t width, uint32_t height);
+void ptDestroyDenoiseGuides(pt_device* device, pt_denoise_guides* guides);
+int  ptRenderDenoiseGuides(pt_device* device, pt_scene* scene, pt_denoise_guides* guides, uint32_t camera_index);
+int  ptReadDenoiseGuides(pt_device* device, pt_denoise_guides* guides, pt_denoise_guide* out);
+int  ptWriteDenoiseGuides(pt_device* device, pt_denoise_guides* guides, const pt_denoise_guide* in);
+/* Enqueues the filter: dst's accumulator := the denoised mean XYZ of src in
+ * .xyz and 1 in .w (0, 0, 0, 0 where src's sample count is not positive), so
+ * ptRenderSampleBuffer, ptReadSampleBuffer and the image writers work on dst
+ * unchanged.  src is not written.  One launch per iteration (step 2^i),
+ * between dst and the guides object's intermediate image (allocated at the
+ * first call with Iterations >= 2); two calls on the same inputs give the
+ * same bits, and the result equals ptsDenoise's (pt_scene.h) bit for bit.
+ * Fails, writing nothing, when src == dst, when src, dst and guides differ in
+ * size or device, when Iterations > 8 or when a sigma is not > 0. */
+int  ptDenoiseSampleBuffer(pt_device* device, pt_sample_buffer* src, pt_denoise_guides* guides,
+                           const pt_denoise_parameters* params, pt_sample_buffer* dst);
+/* The filter kernel of each iteration (no effect on results): AUTO = the
+ * faster one measured per step size, GATHER = every tap from
+ * global memory, LATTICE = one residue class of the step lattice per block,
+ * taps staged in LDS. */
+enum {
+    PT_DENOISE_VARIANT_AUTO    = 0,
+    PT_DENOISE_VARIANT_GATHER  = 1,
+    PT_DENOISE_VARIANT_LATTICE = 2,
+};
+int  ptSetDenoiseVariant(pt_denoise_guides* guides, uint32_t variant);
 
 /* Bit-exact Trace() (scene.glsl.inc:522-611) of n rays: origins (3n floats),
  * packed unit velocities (n), durations (n) -> n hit records. */

@@ -192,8 +192,31 @@ typedef struct pt_scene_packs {
     uint32_t atlas_width, atlas_height, atlas_layer_count;
 } pt_scene_packs;
 
+/* Denoiser records (no reference counterpart), shared by the
+ * device filter (pt_api.h) and the host one (pt_scene.h).
+ *
+ * pt_denoise_guide: the primary hit of a pixel's central camera ray. */
+typedef struct pt_denoise_guide {
+    float    normal[3];                /* UnpackUnitVector(hit.packed_normal); 0,0,0 on a miss */
+    float    time;                     /* hit.time; 0 on a miss */
+    float    albedo[3];                /* linear sRGB base colour (sky colour on a miss) */
+    uint32_t shape;                    /* hit.shape_material >> 16; 0xFFFFFFFF on a miss */
+} pt_denoise_guide;
+
+#define PT_DENOISE_MAX_ITERATIONS 8
+
+typedef struct pt_denoise_parameters {
+    uint32_t Iterations;               /* 0..8, default 5: steps 1, 2, 4, 8, 16 */
+    float    SigmaColor;               /* > 0; halved every iteration */
+    float    SigmaNormal;              /* > 0 */
+    float    SigmaDepth;               /* > 0 */
+    float    SigmaAlbedo;              /* > 0 */
+} pt_denoise_parameters;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(pt_denoise_guide) == 32, "denoise_guide");
+static_assert(sizeof(pt_denoise_parameters) == 20, "denoise_parameters");
 static_assert(sizeof(pt_packed_transform) == 128, "packed_transform");
 static_assert(sizeof(pt_packed_texture) == 32, "packed_texture");
 static_assert(sizeof(pt_packed_shape) == 144, "packed_shape");

@@ -165,6 +165,17 @@ int  ptsSaveSpectrumTable(const char* path);
 int  ptsLoadSpectrumTable(const char* path);
 void ptsSetSpectrumTablePath(const char* path);
 
+/* Edge-avoiding a-trous denoiser on the host (no reference counterpart;
+ * definition in DESIGN.md §6): the CPU path for saved accumulators and the
+ * implementation ptDenoiseSampleBuffer (pt_api.h) is compared with, bit for
+ * bit.  accum_rgba: width*height*4 floats as ptReadSampleBuffer returns them
+ * (XYZ sums + sample count); guides: one record per pixel; out_rgba receives
+ * the denoised mean XYZ and 1 (0, 0, 0, 0 where the count is not positive).
+ * Returns non-zero, leaving out_rgba untouched, on a NULL argument, an empty
+ * image, Iterations > 8 or a sigma that is not > 0.  Single-threaded. */
+int  ptsDenoise(uint32_t width, uint32_t height, const float* accum_rgba, const pt_denoise_guide* guides,
+                const pt_denoise_parameters* params, float* out_rgba);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,13 +15,16 @@ from .scene import (Scene, load_image_rgba8, spectrum_coefficients, build_spectr
 from .integrator import (Device, DeviceScene, SampleBuffer, BasicRenderer, Comm, PathTracerError, ResolveParameters,
                          device_count, CreateSampleBuffer, CreateBasicRenderer, ResetBasicRenderer, RunBasicRenderer,
                          DestroyBasicRenderer, DestroySampleBuffer, RenderSampleBuffer, PreviewParameters,
-                         PreviewRenderContext, CreatePreviewRenderContext, RenderPreview, RetrievePreviewQueryResult)
+                         PreviewRenderContext, CreatePreviewRenderContext, RenderPreview, RetrievePreviewQueryResult,
+                         DenoiseParameters, DenoiseGuides, denoise_host)
 from ._native import (PREVIEW_RENDER_MODE_BASE_COLOR, PREVIEW_RENDER_MODE_BASE_COLOR_SHADED, PREVIEW_RENDER_MODE_NORMAL,
                       PREVIEW_RENDER_MODE_MATERIAL_INDEX, PREVIEW_RENDER_MODE_PRIMITIVE_INDEX,
                       PREVIEW_RENDER_MODE_MESH_COMPLEXITY, PREVIEW_RENDER_MODE_SCENE_COMPLEXITY)
 from ._native import TONE_MAPPING_CLAMP, TONE_MAPPING_REINHARD, TONE_MAPPING_HABLE, TONE_MAPPING_ACES, MAX_SPLIT
 from ._native import (SHADE_DIFFUSE, SHADE_METAL, SHADE_TRANSLUCENT, SHADE_SCATTER, SHADE_OPENPBR, SHADE_PRIMS,
                       SHADE_SKY, SHADE_TEXWRAP)
+from ._native import (DENOISE_GUIDE_DTYPE, DENOISE_MAX_ITERATIONS, DENOISE_VARIANT_AUTO, DENOISE_VARIANT_GATHER,
+                      DENOISE_VARIANT_LATTICE, KERNEL_DENOISE, KERNEL_GUIDES)
 from .image import write_png, write_ppm, write_pfm, read_png
 from .layout import band_rows, owned_pixels
 

@@ -77,6 +77,17 @@ class pt_resolve_parameters(C.Structure):
     ]
 
 
+class pt_denoise_parameters(C.Structure):
+    """pt_denoise_parameters (include/pt_packed.h)."""
+    _fields_ = [
+        ("Iterations", C.c_uint32),
+        ("SigmaColor", C.c_float),
+        ("SigmaNormal", C.c_float),
+        ("SigmaDepth", C.c_float),
+        ("SigmaAlbedo", C.c_float),
+    ]
+
+
 class pt_packed_transform(C.Structure):
     _fields_ = [("To", C.c_float * 16), ("From", C.c_float * 16)]
 
@@ -122,6 +133,10 @@ PREVIEW_AOV_DTYPE = np.dtype([
 ])
 assert PREVIEW_AOV_DTYPE.itemsize == 48
 
+# pt_denoise_guide (include/pt_packed.h): a pixel's primary-hit record for the denoiser.
+DENOISE_GUIDE_DTYPE = np.dtype([("normal", "<f4", (3,)), ("time", "<f4"), ("albedo", "<f4", (3,)), ("shape", "<u4")])
+assert DENOISE_GUIDE_DTYPE.itemsize == 32
+
 # Packed scene layouts (include/pt_packed.h) as numpy dtypes, for tests.
 SHAPE_NODE_DTYPE = np.dtype([("Minimum", "<f4", (3,)), ("ChildNodeIndices", "<u4"),
                              ("Maximum", "<f4", (3,)), ("ShapeIndex", "<u4")])
@@ -156,6 +171,10 @@ KERNEL_PREVIEW = 4
 KERNEL_ROUND = 5     # fused extend + shade (partitions that fit the GPU at once)
 KERNEL_ROUNDS = 6    # a round batch: several rounds of every tile in one launch (PT_KERNEL_ROUNDS)
 MAX_SPLIT = 4        # PT_MAX_SPLIT: tile groups of ptSetBasicRendererSplit
+KERNEL_DENOISE = 7   # one a-trous iteration (PT_KERNEL_DENOISE)
+KERNEL_GUIDES = 8    # ptRenderDenoiseGuides (PT_KERNEL_GUIDES)
+DENOISE_MAX_ITERATIONS = 8
+DENOISE_VARIANT_AUTO, DENOISE_VARIANT_GATHER, DENOISE_VARIANT_LATTICE = 0, 1, 2
 
 _vp = C.c_void_p
 _u32 = C.c_uint32
@@ -219,6 +238,7 @@ SCENE_API = {
     "ptsSaveSpectrumTable": (_i32, [C.c_char_p]),
     "ptsLoadSpectrumTable": (_i32, [C.c_char_p]),
     "ptsSetSpectrumTablePath": (None, [C.c_char_p]),
+    "ptsDenoise": (_i32, [_u32, _u32, _fptr, _vp, C.POINTER(pt_denoise_parameters), _fptr]),
 }
 
 HIP_API = {
@@ -274,6 +294,13 @@ HIP_API = {
     "ptRetrievePreviewQueryResult": (_i32, [_vp, _vp, C.POINTER(C.c_uint32)]),
     "ptReadPreviewImage": (_i32, [_vp, _vp, _fptr]),
     "ptReadPreviewAOVs": (_i32, [_vp, _vp, _vp]),
+    "ptCreateDenoiseGuides": (_vp, [_vp, _u32, _u32]),
+    "ptDestroyDenoiseGuides": (None, [_vp, _vp]),
+    "ptRenderDenoiseGuides": (_i32, [_vp, _vp, _vp, _u32]),
+    "ptReadDenoiseGuides": (_i32, [_vp, _vp, _vp]),
+    "ptWriteDenoiseGuides": (_i32, [_vp, _vp, _vp]),
+    "ptDenoiseSampleBuffer": (_i32, [_vp, _vp, _vp, C.POINTER(pt_denoise_parameters), _vp]),
+    "ptSetDenoiseVariant": (_i32, [_vp, _u32]),
     "ptCheckFastDivision": (_i32, [_vp, C.c_uint64, _u32, C.POINTER(C.c_uint64)]),
     "ptCheckFastReciprocal": (_i32, [_vp, C.POINTER(C.c_uint64)]),
     "ptExtendStats": (_i32, [_vp, _vp, C.POINTER(C.c_uint64)]),

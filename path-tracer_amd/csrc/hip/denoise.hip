@@ -1,0 +1,334 @@
+// denoise.hip — the denoiser in front of the tone mapper (no reference
+// counterpart): guide images taken with the scene's own camera,
+// and the edge-avoiding a-trous filter (Dammertz et al. 2010) over an
+// accumulator-shaped image.
+//
+// Guides: one primary ray per pixel, the central ray of GenerateCameraRay
+// (kernels.hip GenerateNewPath with jitter off and the lens point at the lens
+// centre), through the same Trace() as the extend kernel and the same hit
+// attribute code as ptTraceRays' records; pixels map in 16x16 tiles like the
+// preview kernel.
+//
+// Filter: one launch per iteration between two float4 images (.w = 1: the
+// pixel has a colour, 0: empty).  The per-tap arithmetic is
+// include/pt_denoise.h's, shared with the host implementation
+// (csrc/scene/denoise.cpp); taps run dy outer, dx inner, sums left to right,
+// no atomics.  Two variants of the same function:
+//   gather   every tap read from global memory (25 x 48 B per pixel);
+//   lattice  a block owns a 16x16 set of pixels of ONE residue class of the
+//            step lattice (x = rx, y = ry mod step), so its taps fall in a
+//            20x20 lattice window whatever the step is; the window is staged
+//            in LDS once (400 x 48 B) and the 25 taps read LDS.
+#include "pt_device.hpp"
+#include "traverse.hpp"
+#include "kernels.hpp"
+#include "base_color.hpp"
+#include "../../../include/pt_denoise.h"
+
+namespace ptd {
+
+// --- guides ---------------------------------------------------------------------
+
+struct guide_args {
+    uint32_t camera;
+    uint32_t w, h;
+    uint32_t tiles_x;
+};
+
+// GenerateCameraRay's central ray (kernels.hip:868-894 with SamplePosition =
+// pixel + 0.5 and the lens point O = 0: no random number), then the packed
+// velocity round trip every ray of the integrator takes between raygen and
+// extend (TileOrderStoreRay / ray_source_slots::load).  False: unknown model.
+PT_DEV bool CentralCameraRay(const dscene& S, const guide_args& P, uint32_t x, uint32_t y, pt3& RO, pt3& RV)
+{
+    float SPx = (float)x, SPy = (float)y;
+    SPx = SPx + 0.5f; SPy = SPy + 0.5f;
+    float Nx = SPx / (float)P.w, Ny = SPy / (float)P.h;
+    const pt_packed_camera* Cam = &S.cameras[P.camera];
+    uint32_t Model = Cam->Model;
+    pt3 O, V;
+    if (Model == PT_CAMERA_MODEL_PINHOLE || Model == PT_CAMERA_MODEL_THIN_LENS) {
+        pt3 SP = v3(-Cam->SensorSize[0] * (Nx - 0.5f), -Cam->SensorSize[1] * (0.5f - Ny), Cam->SensorDistance);
+        O = v3(0, 0, 0);
+        if (Model == PT_CAMERA_MODEL_PINHOLE) {
+            V = normalize(O - SP);
+        } else {
+            pt3 OP = -SP * Cam->FocalLength / (SP.z - Cam->FocalLength);
+            V = normalize(OP - O);
+        }
+    } else if (Model == PT_CAMERA_MODEL_360) {
+        float Phi = (Nx - 0.5f) * PT_TAU;
+        float Theta = (0.5f - Ny) * PT_PI;
+        O = v3(0, 0, 0);
+        V = v3(pt_cos(Theta) * pt_sin(Phi), pt_sin(Theta), -pt_cos(Theta) * pt_cos(Phi));
+    } else {
+        RO = v3s(0); RV = v3(0, 0, 1);
+        return false;
+    }
+    const float* To = Cam->Transform.To;
+    RO = mat4_mul_point(To, O);
+    RV = UnpackUnitVector(PackUnitVector(mat4_mul_vector(To, V)));
+    return true;
+}
+
+struct ray_source_guides {
+    const dscene* S;
+    const guide_args* P;
+    PT_DEV bool pixel(uint32_t i, uint32_t& x, uint32_t& y) const
+    {
+        uint32_t t = i >> 8, l = i & 255u;
+        uint32_t ty = t / P->tiles_x;
+        x = (t - ty * P->tiles_x) * 16 + (l & 15u);
+        y = ty * 16 + (l >> 4);
+        return x < P->w && y < P->h;
+    }
+    PT_DEV bool load(uint32_t i, pt3& O, pt3& V, float& D) const
+    {
+        uint32_t x, y;
+        pixel(i, x, y);
+        D = PT_HIT_TIME_LIMIT;
+        return CentralCameraRay(*S, *P, x, y, O, V);
+    }
+};
+
+// A guide record as two float4: {normal, time}, {albedo, shape bits}.
+template <int CAP>
+__global__ __launch_bounds__(256) void guides_kernel(dscene S, guide_args P, uint32_t* spill, uint32_t spill_stride,
+                                                     float4* __restrict__ out,
+                                                     const observe_table* __restrict__ observe)
+{
+    __shared__ uint32_t smem[CAP * 256];
+    const observe_table& Tb = *observe;
+    uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    ray_source_guides src{&S, &P};
+    uint32_t x, y;
+    if (!src.pixel(i, x, y)) return;
+    tstack<true, CAP> st;
+    st.lds = &smem[threadIdx.x];
+    st.spill = spill ? spill + i : nullptr;
+    st.stride = spill_stride;
+
+    pt3 O, V;
+    float D;
+    const bool known = src.load(i, O, V, D);
+    lane_state Ln;
+    LaneBegin(S, Ln, O, V, D);
+    complexity_stats cx;
+    if (known && S.g.ShapeCount != 0)
+        while (!LaneStep<true, CAP>(S, Ln, st, src, i, cx)) {}
+
+    size_t p = (size_t)y * P.w + x;
+    if (Ln.Shape == SHAPE_INDEX_NONE) {
+        pt3 A = v3s(0);
+        if (known) A = XYZToSRGB(ObserveUnderD65(Tb, SampleSkyboxSpectrum(S, V)));
+        out[2 * p] = make_float4(0, 0, 0, 0);
+        out[2 * p + 1] = make_float4(A.x, A.y, A.z, __uint_as_float(0xFFFFFFFFu));
+        return;
+    }
+    // The ptTraceRays record (finalize_kernel): compact hit -> attributes ->
+    // {time, shape << 16 | material, packed normal}; the guide unpacks it.
+    float4 h = CompactHit(Ln, S.vidx21 != 0);
+    float2 c = make_float2(Ln.C.y, Ln.C.z);
+    uint32_t Material;
+    pt3 N, TX;
+    pt2 UV;
+    HitAttributesRecord(S, Ln.Shape, h, c, Material, N, TX, UV);
+    uint32_t ShapeMaterial = (Ln.Shape << 16) | Material;
+    pt3 Nq = UnpackUnitVector(PackUnitVector(N));
+    pt3 A = XYZToSRGB(MaterialBaseColor(S, Tb, Material, UV));
+    out[2 * p] = make_float4(Nq.x, Nq.y, Nq.z, h.x);
+    out[2 * p + 1] = make_float4(A.x, A.y, A.z, __uint_as_float(ShapeMaterial >> 16));
+}
+
+// --- filter ---------------------------------------------------------------------
+
+struct denoise_args {
+    uint32_t w, h;
+    uint32_t step;
+    pt_denoise_sigmas sg;
+    // lattice variant: residue classes and 16x16 lattice tiles per class
+    uint32_t ncx, ncy;
+};
+
+// FIRST: the input is the accumulator (XYZ sums, sample count); the filter's
+// c_0 is formed on load.
+template <bool FIRST>
+PT_DEV float4 LoadColor(const float4* __restrict__ in, size_t i)
+{
+    float4 v = in[i];
+    if (!FIRST) return v;
+    if (v.w > 0.0f) return make_float4(v.x / v.w, v.y / v.w, v.z / v.w, 1.0f);
+    return make_float4(0, 0, 0, 0);
+}
+
+PT_DEV pt_denoise_pixel MakePixel(float4 c, float4 ga, float4 gb)
+{
+    pt_denoise_pixel p;
+    p.c.x = c.x; p.c.y = c.y; p.c.z = c.z;
+    p.n.x = ga.x; p.n.y = ga.y; p.n.z = ga.z;
+    p.t = ga.w;
+    p.a.x = gb.x; p.a.y = gb.y; p.a.z = gb.z;
+    p.shape = __float_as_uint(gb.w);
+    return p;
+}
+
+struct tap_sums { float x, y, z, w; };
+
+// One tap that lies inside the image: skipped when empty or of another shape.
+PT_DEV void Tap(tap_sums& A, const pt_denoise_pixel& p, float4 c, float4 ga, float4 gb, int dx, int dy,
+                const pt_denoise_sigmas& sg)
+{
+    if (!(c.w > 0.0f) || __float_as_uint(gb.w) != p.shape) return;
+    pt_denoise_pixel q = MakePixel(c, ga, gb);
+    float hk = pt_denoise_k(dx + 2) * pt_denoise_k(dy + 2);
+    float w = pt_denoise_weight(hk, &p, &q, &sg);
+    A.x = A.x + w * q.c.x;
+    A.y = A.y + w * q.c.y;
+    A.z = A.z + w * q.c.z;
+    A.w = A.w + w;
+}
+
+template <bool FIRST>
+__global__ __launch_bounds__(256) void denoise_gather_kernel(const float4* __restrict__ in,
+                                                             const float4* __restrict__ guides, denoise_args P,
+                                                             float4* __restrict__ out)
+{
+    const uint32_t x = blockIdx.x * 16 + (threadIdx.x & 15u), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (x >= P.w || y >= P.h) return;
+    const size_t ip = (size_t)y * P.w + x;
+    float4 cp = LoadColor<FIRST>(in, ip);
+    if (!(cp.w > 0.0f)) { out[ip] = make_float4(0, 0, 0, 0); return; }
+    const pt_denoise_pixel p = MakePixel(cp, guides[2 * ip], guides[2 * ip + 1]);
+    tap_sums A{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int dy = -2; dy <= 2; dy++) {
+        const int64_t qy = (int64_t)y + (int64_t)dy * (int64_t)P.step;
+        if (qy < 0 || qy >= (int64_t)P.h) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int64_t qx = (int64_t)x + (int64_t)dx * (int64_t)P.step;
+            if (qx < 0 || qx >= (int64_t)P.w) continue;
+            const size_t iq = (size_t)qy * P.w + (size_t)qx;
+            Tap(A, p, LoadColor<FIRST>(in, iq), guides[2 * iq], guides[2 * iq + 1], dx, dy, P.sg);
+        }
+    }
+    out[ip] = make_float4(A.x / A.w, A.y / A.w, A.z / A.w, 1.0f);
+}
+
+// LDS window: 20 rows of 20 records in three 16-B arrays (colour, {normal,
+// time}, {albedo, shape}), row stride 32 records = 512 B.  A wave reads 4
+// window rows x 16 consecutive records per tap with ds_read_b128, whose
+// 16-lane groups each take 8 + 4 + 4 lanes of two neighbouring rows; a row
+// stride that is a multiple of the 256-B bank row puts those pieces on
+// disjoint 16-B slots (a packed 320-B stride would overlap them).
+constexpr uint32_t DN_WIN = 20;
+constexpr uint32_t DN_ROW = 32;
+
+template <bool FIRST>
+__global__ __launch_bounds__(256) void denoise_lattice_kernel(const float4* __restrict__ in,
+                                                              const float4* __restrict__ guides, denoise_args P,
+                                                              float4* __restrict__ out)
+{
+    __shared__ float4 sc[DN_WIN * DN_ROW], sa[DN_WIN * DN_ROW], sb[DN_WIN * DN_ROW];
+    // Neighbouring blocks take neighbouring residues of the same lattice
+    // tile: their strided window loads share cache lines.
+    const uint32_t tile_x = blockIdx.x / P.ncx, rx = blockIdx.x - tile_x * P.ncx;
+    const uint32_t tile_y = blockIdx.y / P.ncy, ry = blockIdx.y - tile_y * P.ncy;
+    for (uint32_t r = threadIdx.x; r < DN_WIN * DN_WIN; r += 256) {
+        const uint32_t wy = r / DN_WIN, wx = r - wy * DN_WIN;
+        // lattice coordinates of the record; the window starts 2 before the tile
+        const int64_t lx = (int64_t)(tile_x * 16 + wx) - 2, ly = (int64_t)(tile_y * 16 + wy) - 2;
+        const int64_t qx = (int64_t)rx + lx * (int64_t)P.step, qy = (int64_t)ry + ly * (int64_t)P.step;
+        float4 c = make_float4(0, 0, 0, 0), ga = c, gb = c;
+        if (lx >= 0 && ly >= 0 && qx < (int64_t)P.w && qy < (int64_t)P.h) {
+            const size_t iq = (size_t)qy * P.w + (size_t)qx;
+            c = LoadColor<FIRST>(in, iq);
+            ga = guides[2 * iq];
+            gb = guides[2 * iq + 1];
+        }
+        sc[wy * DN_ROW + wx] = c;      // outside the image: .w = 0, skipped like an empty pixel
+        sa[wy * DN_ROW + wx] = ga;
+        sb[wy * DN_ROW + wx] = gb;
+    }
+    __syncthreads();
+    const uint32_t tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+    const uint64_t x = (uint64_t)rx + (uint64_t)(tile_x * 16 + tx) * P.step;
+    const uint64_t y = (uint64_t)ry + (uint64_t)(tile_y * 16 + ty) * P.step;
+    if (x >= P.w || y >= P.h) return;
+    const size_t ip = (size_t)y * P.w + (size_t)x;
+    const uint32_t ic = (ty + 2) * DN_ROW + tx + 2;
+    float4 cp = sc[ic];
+    if (!(cp.w > 0.0f)) { out[ip] = make_float4(0, 0, 0, 0); return; }
+    const pt_denoise_pixel p = MakePixel(cp, sa[ic], sb[ic]);
+    tap_sums A{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const uint32_t iq = (uint32_t)((int)ic + dy * (int)DN_ROW + dx);
+            Tap(A, p, sc[iq], sa[iq], sb[iq], dx, dy, P.sg);
+        }
+    }
+    out[ip] = make_float4(A.x / A.w, A.y / A.w, A.z / A.w, 1.0f);
+}
+
+// Iterations = 0: the accumulator's mean, .w = 1 (0, 0, 0, 0 where empty).
+__global__ __launch_bounds__(256) void denoise_mean_kernel(const float4* __restrict__ accum, uint32_t n,
+                                                           float4* __restrict__ out)
+{
+    uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    out[i] = LoadColor<true>(accum, i);
+}
+
+}  // namespace ptd
+
+uint32_t pt_guides_stack_cap() { return 20; }
+
+hipError_t pt_launch_denoise_guides(const ptd::dscene& S, uint32_t camera_index, uint32_t w, uint32_t h,
+                                    uint32_t* spill, float4* guides, const float* observe_table, hipStream_t st)
+{
+    ptd::guide_args P;
+    P.camera = camera_index;
+    P.w = w;
+    P.h = h;
+    P.tiles_x = (w + 15) / 16;
+    uint32_t tiles = P.tiles_x * ((h + 15) / 16);
+    if (tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(ptd::guides_kernel<20>, dim3(tiles), dim3(256), 0, st, S, P, spill, tiles * 256, guides,
+                       reinterpret_cast<const ptd::observe_table*>(observe_table));
+    return hipGetLastError();
+}
+
+hipError_t pt_launch_denoise(const float4* in, bool accumulator, const float4* guides, uint32_t w, uint32_t h,
+                             const pt_denoise_parameters* p, uint32_t iteration, bool lattice, float4* out,
+                             hipStream_t st)
+{
+    if (w == 0 || h == 0) return hipSuccess;
+    ptd::denoise_args P;
+    P.w = w;
+    P.h = h;
+    P.step = 1u << iteration;
+    P.sg = pt_denoise_iteration_sigmas(p, iteration);
+    P.ncx = P.step < w ? P.step : w;
+    P.ncy = P.step < h ? P.step : h;
+    if (lattice) {
+        // 16x16 lattice tiles of the largest residue class (rx = ry = 0); the
+        // smaller classes leave their last tiles partly or wholly idle.
+        uint32_t lw = (w + P.step - 1) / P.step, lh = (h + P.step - 1) / P.step;
+        dim3 grid(P.ncx * ((lw + 15) / 16), P.ncy * ((lh + 15) / 16));
+        if (accumulator) hipLaunchKernelGGL(ptd::denoise_lattice_kernel<true>, grid, dim3(256), 0, st, in, guides, P, out);
+        else hipLaunchKernelGGL(ptd::denoise_lattice_kernel<false>, grid, dim3(256), 0, st, in, guides, P, out);
+    } else {
+        dim3 grid((w + 15) / 16, (h + 15) / 16);
+        if (accumulator) hipLaunchKernelGGL(ptd::denoise_gather_kernel<true>, grid, dim3(256), 0, st, in, guides, P, out);
+        else hipLaunchKernelGGL(ptd::denoise_gather_kernel<false>, grid, dim3(256), 0, st, in, guides, P, out);
+    }
+    return hipGetLastError();
+}
+
+hipError_t pt_launch_denoise_mean(const float4* accum, uint32_t n, float4* out, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(ptd::denoise_mean_kernel, dim3((n + 255) / 256), dim3(256), 0, st, accum, n, out);
+    return hipGetLastError();
+}

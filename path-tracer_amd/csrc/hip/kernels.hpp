@@ -110,6 +110,21 @@ hipError_t pt_launch_preview(const ptd::dscene& S, const pt_preview_parameters* 
 uint32_t pt_preview_stack_cap();
 hipError_t pt_launch_resolve(const float4* accum, uint32_t n, float brightness, uint32_t mode, float white, float4* out,
                              uint32_t* out8, hipStream_t st);
+// Denoiser (denoise.hip).  Guides: one central camera ray per pixel of a
+// w x h frame -> 2 float4 per pixel ({normal, time}, {albedo, shape}: a
+// pt_denoise_guide); spill as for the preview (pt_guides_stack_cap).
+hipError_t pt_launch_denoise_guides(const ptd::dscene& S, uint32_t camera_index, uint32_t w, uint32_t h,
+                                    uint32_t* spill, float4* guides, const float* observe_table, hipStream_t st);
+uint32_t pt_guides_stack_cap();
+// One a-trous iteration (step 2^iteration) in -> out.  accumulator: `in` is
+// a sample buffer's accumulator (iteration 0), else a filtered image.
+// lattice: the LDS-staged residue-class kernel, else the global gather; both
+// compute the same bits.
+hipError_t pt_launch_denoise(const float4* in, bool accumulator, const float4* guides, uint32_t w, uint32_t h,
+                             const pt_denoise_parameters* p, uint32_t iteration, bool lattice, float4* out,
+                             hipStream_t st);
+// Iterations = 0: out = the accumulator's mean, .w = 1 (zeros where empty).
+hipError_t pt_launch_denoise_mean(const float4* accum, uint32_t n, float4* out, hipStream_t st);
 // compact: the completion-queue instantiation (ShadeTile), for scenes whose
 // paths also end at surfaces.
 hipError_t pt_launch_shade(const ptd::dscene& S, const ptd::dslots& L, const ptd::dframe& F, const ptd::dparams& P,

@@ -1,0 +1,83 @@
+// denoise.cpp — ptsDenoise (include/pt_scene.h): the edge-avoiding a-trous
+// filter of DESIGN.md §6 on the host.  The CPU path for saved accumulators
+// and the second implementation the device kernels (csrc/hip/denoise.hip) are
+// compared with: the same definition, the same per-tap arithmetic
+// (include/pt_denoise.h), the same tap order.  Single-threaded.
+#include "../../../include/pt_scene.h"
+#include "../../../include/pt_denoise.h"
+
+#include <cstring>
+#include <new>
+#include <vector>
+
+namespace {
+
+struct px4 { float x, y, z, w; };   // w: 1 = pixel has a colour, 0 = empty
+
+pt_denoise_pixel Pixel(const px4& c, const pt_denoise_guide& g)
+{
+    pt_denoise_pixel p;
+    p.c = {c.x, c.y, c.z};
+    p.n = {g.normal[0], g.normal[1], g.normal[2]};
+    p.t = g.time;
+    p.a = {g.albedo[0], g.albedo[1], g.albedo[2]};
+    p.shape = g.shape;
+    return p;
+}
+
+void Iterate(uint32_t W, uint32_t H, const px4* in, const pt_denoise_guide* guides, const pt_denoise_sigmas& sg,
+             uint32_t step, px4* out)
+{
+    for (uint32_t y = 0; y < H; y++) {
+        for (uint32_t x = 0; x < W; x++) {
+            const size_t ip = (size_t)y * W + x;
+            if (!(in[ip].w > 0.0f)) { out[ip] = {0, 0, 0, 0}; continue; }
+            const pt_denoise_pixel p = Pixel(in[ip], guides[ip]);
+            float sx = 0.0f, sy = 0.0f, sz = 0.0f, sw = 0.0f;
+            for (int dy = -2; dy <= 2; dy++) {
+                const int64_t qy = (int64_t)y + (int64_t)dy * step;
+                if (qy < 0 || qy >= (int64_t)H) continue;
+                for (int dx = -2; dx <= 2; dx++) {
+                    const int64_t qx = (int64_t)x + (int64_t)dx * step;
+                    if (qx < 0 || qx >= (int64_t)W) continue;
+                    const size_t iq = (size_t)qy * W + (size_t)qx;
+                    if (!(in[iq].w > 0.0f) || guides[iq].shape != p.shape) continue;
+                    const pt_denoise_pixel q = Pixel(in[iq], guides[iq]);
+                    const float h = pt_denoise_k(dx + 2) * pt_denoise_k(dy + 2);
+                    const float w = pt_denoise_weight(h, &p, &q, &sg);
+                    sx = sx + w * q.c.x;
+                    sy = sy + w * q.c.y;
+                    sz = sz + w * q.c.z;
+                    sw = sw + w;
+                }
+            }
+            out[ip] = {sx / sw, sy / sw, sz / sw, 1.0f};
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int ptsDenoise(uint32_t width, uint32_t height, const float* accum_rgba, const pt_denoise_guide* guides,
+                          const pt_denoise_parameters* params, float* out_rgba)
+{
+    if (!accum_rgba || !guides || !params || !out_rgba || width == 0 || height == 0) return -1;
+    if (!pt_denoise_parameters_ok(params)) return -1;
+    const size_t n = (size_t)width * height;
+    try {
+        std::vector<px4> a(n), b(params->Iterations ? n : 0);
+        for (size_t i = 0; i < n; i++) {
+            const float* s = accum_rgba + 4 * i;
+            if (s[3] > 0.0f) a[i] = {s[0] / s[3], s[1] / s[3], s[2] / s[3], 1.0f};
+            else a[i] = {0, 0, 0, 0};
+        }
+        for (uint32_t i = 0; i < params->Iterations; i++) {
+            Iterate(width, height, a.data(), guides, pt_denoise_iteration_sigmas(params, i), 1u << i, b.data());
+            a.swap(b);
+        }
+        std::memcpy(out_rgba, a.data(), n * sizeof(px4));
+    } catch (const std::bad_alloc&) {
+        return -2;
+    }
+    return 0;
+}

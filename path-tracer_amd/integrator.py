@@ -174,6 +174,87 @@ class ResolveParameters:
         return N.pt_resolve_parameters(self.Brightness, self.ToneMappingMode, self.ToneMappingWhiteLevel)
 
 
+class DenoiseParameters:
+    """pt_denoise_parameters (pt_packed.h): the a-trous filter's iteration
+    count (steps 1, 2, 4, ... 2^(Iterations-1)) and edge-stopping sigmas.  The
+    defaults are the ones chosen on configs 1 and 3, 8 spp against 512 spp
+    (DESIGN.md §6)."""
+
+    def __init__(self, Iterations: int = 5, SigmaColor: float = 0.5, SigmaNormal: float = 0.25,
+                 SigmaDepth: float = 0.3, SigmaAlbedo: float = 0.1):
+        self.Iterations = int(Iterations)
+        self.SigmaColor, self.SigmaNormal = float(SigmaColor), float(SigmaNormal)
+        self.SigmaDepth, self.SigmaAlbedo = float(SigmaDepth), float(SigmaAlbedo)
+
+    def as_struct(self) -> N.pt_denoise_parameters:
+        return N.pt_denoise_parameters(self.Iterations, self.SigmaColor, self.SigmaNormal, self.SigmaDepth,
+                                       self.SigmaAlbedo)
+
+
+def denoise_host(accum: np.ndarray, guides: np.ndarray, params: "DenoiseParameters | None" = None) -> np.ndarray:
+    """The denoiser on the CPU (ptsDenoise, libptscene.so): for saved
+    accumulators on a machine without a GPU, and the implementation the
+    device filter equals bit for bit.  accum: (H, W, 4) XYZ sums + sample
+    count; guides: (H, W) DENOISE_GUIDE_DTYPE records.  Returns (H, W, 4):
+    the denoised mean XYZ and 1 (zeros where the count is not positive)."""
+    a = np.ascontiguousarray(accum, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"accumulator of shape {a.shape}, expected (H, W, 4)")
+    g = np.ascontiguousarray(guides, dtype=N.DENOISE_GUIDE_DTYPE)
+    if g.shape != a.shape[:2]:
+        raise ValueError(f"guides of shape {g.shape}, accumulator {a.shape[:2]}")
+    out = np.zeros_like(a)
+    p = (params or DenoiseParameters()).as_struct()
+    rc = N.scene_lib().ptsDenoise(a.shape[1], a.shape[0], N.fptr(a), g.ctypes.data, C.byref(p), N.fptr(out))
+    if rc != 0:
+        raise PathTracerError(f"ptsDenoise: bad arguments (status {rc})")
+    return out
+
+
+class DenoiseGuides:
+    """Per-pixel primary-hit records of the scene camera's central rays
+    (normal, hit time, base colour, shape) that steer the denoiser, plus the
+    filter's intermediate image (ptCreateDenoiseGuides)."""
+
+    def __init__(self, device: "Device", width: int, height: int):
+        L = N.hip_lib()
+        self.device = device
+        self.width, self.height = int(width), int(height)
+        self._h = L.ptCreateDenoiseGuides(device.handle, self.width, self.height)
+        if not self._h:
+            raise PathTracerError(L.ptGetLastError().decode())
+
+    @property
+    def handle(self):
+        return self._h
+
+    def render(self, scene: "DeviceScene", camera_index: int = 0):
+        """One central camera ray per pixel of packed camera `camera_index` (enqueues)."""
+        _check(N.hip_lib().ptRenderDenoiseGuides(self.device.handle, scene.handle, self._h, int(camera_index)),
+               "ptRenderDenoiseGuides")
+
+    def read(self) -> np.ndarray:
+        out = np.zeros((self.height, self.width), dtype=N.DENOISE_GUIDE_DTYPE)
+        _check(N.hip_lib().ptReadDenoiseGuides(self.device.handle, self._h, out.ctypes.data), "ptReadDenoiseGuides")
+        return out
+
+    def write(self, guides: np.ndarray):
+        g = np.ascontiguousarray(guides, dtype=N.DENOISE_GUIDE_DTYPE)
+        if g.size != self.width * self.height:
+            raise ValueError(f"guides have {g.size} pixels, the object {self.width * self.height}")
+        _check(N.hip_lib().ptWriteDenoiseGuides(self.device.handle, self._h, g.ctypes.data), "ptWriteDenoiseGuides")
+
+    def set_variant(self, variant: int):
+        """DENOISE_VARIANT_AUTO / _GATHER / _LATTICE: the filter kernel used
+        (identical results; ptSetDenoiseVariant)."""
+        _check(N.hip_lib().ptSetDenoiseVariant(self._h, int(variant)), "ptSetDenoiseVariant")
+
+    def close(self):
+        if self._h:
+            N.hip_lib().ptDestroyDenoiseGuides(self.device.handle, self._h)
+            self._h = None
+
+
 class SampleBuffer:
     """rgba32f accumulator: CIE XYZ sums + sample count (integrator.cpp:15-87)."""
 
@@ -203,6 +284,23 @@ class SampleBuffer:
         """RenderSampleBuffer (integrator.hpp:55-60): resolve on the device."""
         p = (params or ResolveParameters(**kw)).as_struct()
         _check(N.hip_lib().ptRenderSampleBuffer(self.device.handle, self._h, C.byref(p)), "ptRenderSampleBuffer")
+
+    def denoise(self, guides: "DenoiseGuides", params: "DenoiseParameters | None" = None,
+                out: "SampleBuffer | None" = None) -> "SampleBuffer":
+        """The edge-avoiding a-trous filter on the device (ptDenoiseSampleBuffer;
+        enqueues): `out` (a new sample buffer of this size when None) receives
+        the denoised mean XYZ and a sample count of 1, so out.render(...) and
+        out.read() work as on any sample buffer.  This buffer is not written."""
+        dst = out if out is not None else SampleBuffer(self.device, self.width, self.height)
+        p = (params or DenoiseParameters()).as_struct()
+        try:
+            _check(N.hip_lib().ptDenoiseSampleBuffer(self.device.handle, self._h, guides.handle, C.byref(p),
+                                                     dst.handle), "ptDenoiseSampleBuffer")
+        except PathTracerError:
+            if out is None:
+                dst.close()
+            raise
+        return dst
 
     def read_resolved(self) -> np.ndarray:
         """OutColor of the last render(): (H, W, 4) float32, alpha 1."""

@@ -10,11 +10,16 @@
 * OpenPBR shading (opt-in, §6 row 4): Mrays/s of the layered OpenPBR scene
   of tests/test_openpbr.py at 1920x1080, shaded, against the same scene with
   OpenPBR hits ending the path (the reference's behaviour).
+* denoise (ptDenoiseSampleBuffer, denoise.hip): ms per a-trous
+  iteration (step 1 .. 32) of the gather and the lattice kernel and of the
+  automatic choice, ms per 5-iteration call, and the guide kernel, on C3 at
+  1920x1080 and 3840x2160.
 * host builds (§8(f) row 3): mesh BVH build of a 1.96 M-face mesh on 1 and
   on all of the job's threads, and the RGB -> spectrum table.
 
 Kernel times are HIP events on the device stream (ptGetKernelStats).
-Prints one JSON object.
+Prints one JSON object.  usage: bench_next.py [resolve|denoise|preview|openpbr|host ...]
+(default: all).
 """
 import json
 import os
@@ -31,6 +36,7 @@ from exp_reorder import load  # noqa: E402
 
 HBM_GBPS = 8000.0
 K_RESOLVE, K_PREVIEW, K_EXTEND, K_SHADE, K_ROUND = 3, 4, 1, 2, 5
+K_DENOISE, K_GUIDES = 7, 8
 
 
 def timed(dev, kernel, fn, reps):
@@ -66,6 +72,46 @@ def resolve(pt, dev):
             out[f"{W}x{H}_{name}"] = {"ms": round(ms, 4), "gbps": round(gbps, 1), "frac": round(gbps / HBM_GBPS, 3)}
         r.close()
         sb.close()
+    ds.close()
+    return out
+
+
+def denoise(pt, dev):
+    """Per size: guides_ms; per variant the kernel time of each step (the
+    difference between the summed launches of k and of k - 1 iterations: an
+    iteration's step and constants depend on its index only) and of a
+    5-iteration call, with its wall time."""
+    out = {}
+    scene = pt.Scene.config(3)
+    ds = pt.DeviceScene(dev)
+    ds.update(scene)
+    variants = {"gather": pt.DENOISE_VARIANT_GATHER, "lattice": pt.DENOISE_VARIANT_LATTICE,
+                "auto": pt.DENOISE_VARIANT_AUTO}
+    for W, H in ((1920, 1080), (3840, 2160)):
+        sb, dst = pt.SampleBuffer(dev, W, H), pt.SampleBuffer(dev, W, H)
+        r = pt.BasicRenderer(dev, ds, sb)
+        r.RenderFlags = 3
+        r.reset()
+        r.run(8)
+        guides = pt.DenoiseGuides(dev, W, H)
+        guides.render(ds, 0)   # warm
+        gms, _ = timed(dev, K_GUIDES, lambda: guides.render(ds, 0), 10)
+        res = {"guides_ms": round(gms, 4)}
+        for name, variant in variants.items():
+            guides.set_variant(variant)
+            total = [0.0]
+            for k in range(1, 7):
+                p = pt.DenoiseParameters(Iterations=k)
+                sb.denoise(guides, p, out=dst)   # warm (and the intermediate image's allocation)
+                ms, wall = timed(dev, K_DENOISE, lambda: sb.denoise(guides, p, out=dst), 10)
+                total.append(ms * k)             # timed() returns ms per launch
+                if k == 5:
+                    res[f"{name}_call5_ms"] = round(ms * k, 4)
+                    res[f"{name}_call5_wall_ms"] = round(wall, 4)
+            res[f"{name}_step_ms"] = {str(1 << (k - 1)): round(total[k] - total[k - 1], 4) for k in range(1, 7)}
+        out[f"{W}x{H}"] = res
+        for x in (guides, r, dst, sb):
+            x.close()
     ds.close()
     return out
 
@@ -149,10 +195,13 @@ def host_builds(pt):
 
 def main():
     pt = load()
+    entries = {"resolve": resolve, "denoise": denoise, "preview": preview, "openpbr": openpbr}
+    want = sys.argv[1:] or list(entries) + ["host"]
     dev = pt.Device(0)
-    res = {"resolve": resolve(pt, dev), "preview": preview(pt, dev), "openpbr": openpbr(pt, dev)}
+    res = {name: fn(pt, dev) for name, fn in entries.items() if name in want}
     dev.close()
-    res["host"] = host_builds(pt)
+    if "host" in want:
+        res["host"] = host_builds(pt)
     print(json.dumps(res), flush=True)
 
 

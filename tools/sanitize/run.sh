@@ -36,6 +36,7 @@ done
 run asan_models "$A" model $(ls -d "$C"/models/m*/ | while read d; do ls "$d"*.obj; done) "$C"/models/*.obj
 run asan_scenes "$A" scene $(ls -d "$C"/scenes/s*/ | sed 's|$|scene.json|') "$C/scenes/src/scene.json"
 run asan_render "$A" render
+run asan_denoise "$A" denoise
 PT_BVH_THREADS=8 run tsan_bvh "$T" bvh 300000
 run tsan_render "$T" render
 PT_BVH_THREADS=8 run asan_bvh "$A" bvh 200000

@@ -14,10 +14,14 @@
 //                               on small frames, resolve, preview
 //   san_driver bvh FACES        random triangle soup through CreateMesh (the
 //                               threaded builder, PT_BVH_THREADS) + PackSceneData
+//   san_driver denoise          ptsDenoise on random small images: sizes below
+//                               the 2 * step halo, every iteration count, an
+//                               all-empty image, rejected arguments
 #include "../../path-tracer_amd/csrc/scene/scene.hpp"
 #include "../../path-tracer_amd/csrc/scene/configs.hpp"
 #include "../../path-tracer_amd/csrc/scene/image.hpp"
 #include "../../oracle/pt_oracle.h"
+#include "../../include/pt_scene.h"
 
 #include <cstdio>
 #include <cstring>
@@ -165,15 +169,60 @@ static int Bvh(uint32_t faces)
     return 0;
 }
 
+static int Denoise()
+{
+    std::mt19937 rng(11);
+    std::uniform_real_distribution<float> u(0.0f, 4.0f), s(-1.0f, 1.0f);
+    const uint32_t sizes[][2] = {{1, 1}, {1, 7}, {3, 2}, {5, 5}, {16, 16}, {17, 33}, {40, 24}, {67, 45}};
+    for (auto& wh : sizes) {
+        const uint32_t W = wh[0], H = wh[1];
+        const size_t n = (size_t)W * H;
+        for (int empty = 0; empty < 2; empty++) {
+            std::vector<float> acc(4 * n), out(4 * n, -1.0f);
+            std::vector<pt_denoise_guide> g(n);
+            for (size_t i = 0; i < n; i++) {
+                for (int k = 0; k < 3; k++) acc[4 * i + k] = u(rng);
+                acc[4 * i + 3] = empty ? 0.0f : (float)(rng() % 5);   // some pixels empty
+                for (int k = 0; k < 3; k++) { g[i].normal[k] = s(rng); g[i].albedo[k] = 0.5f * u(rng); }
+                g[i].time = 1.0f + u(rng);
+                g[i].shape = rng() % 4 == 0 ? 0xFFFFFFFFu : rng() % 3;
+            }
+            for (uint32_t it = 0; it <= 8; it++) {
+                pt_denoise_parameters p{it, 1.0f, 0.5f, 0.5f, 0.5f};
+                if (ptsDenoise(W, H, acc.data(), g.data(), &p, out.data()) != 0) { std::printf("denoise: failed\n"); return 1; }
+                size_t filled = 0;
+                for (size_t i = 0; i < n; i++) filled += out[4 * i + 3] == 1.0f;
+                std::printf("denoise %ux%u empty %d iterations %u: %zu of %zu pixels\n", W, H, empty, it, filled, n);
+            }
+        }
+    }
+    // rejected arguments leave `out` untouched
+    float acc[4] = {1, 1, 1, 1}, out[4] = {7, 7, 7, 7};
+    pt_denoise_guide g{};
+    pt_denoise_parameters ok{5, 1, 1, 1, 1}, many{9, 1, 1, 1, 1}, zero{5, 1, 0, 1, 1};
+    int bad = 0;
+    bad += ptsDenoise(1, 1, nullptr, &g, &ok, out) == 0;
+    bad += ptsDenoise(1, 1, acc, nullptr, &ok, out) == 0;
+    bad += ptsDenoise(1, 1, acc, &g, nullptr, out) == 0;
+    bad += ptsDenoise(1, 1, acc, &g, &ok, nullptr) == 0;
+    bad += ptsDenoise(1, 1, acc, &g, &many, out) == 0;
+    bad += ptsDenoise(1, 1, acc, &g, &zero, out) == 0;
+    bad += ptsDenoise(0, 1, acc, &g, &ok, out) == 0;
+    for (float v : out) bad += v != 7.0f;
+    std::printf("denoise: %d argument checks wrong\n", bad);
+    return bad != 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh ...\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise ...\n"); return 2; }
     std::string cmd = argv[1];
     if (cmd == "decode") return Decode(argc - 2, argv + 2);
     if (cmd == "model") return Model(argc - 2, argv + 2);
     if (cmd == "scene") return Scene(argc - 2, argv + 2);
     if (cmd == "render") return Render();
     if (cmd == "bvh") return Bvh(argc > 2 ? (uint32_t)std::strtoul(argv[2], nullptr, 10) : 200000u);
+    if (cmd == "denoise") return Denoise();
     std::fprintf(stderr, "unknown command %s\n", cmd.c_str());
     return 2;
 }
