@@ -27,8 +27,10 @@
  * Additions (no reference counterpart): sample-buffer readback, explicit
  * synchronisation, a bit-exact ray query (ptTraceRays), slot-state readback,
  * per-kernel timing, pixel-band partitioning, an RCCL frame-end reduce for
- * one-process-per-GPU rendering, and a denoiser (guide images + an
- * edge-avoiding a-trous filter) in front of ptRenderSampleBuffer.
+ * one-process-per-GPU rendering, a denoiser (guide images + an
+ * edge-avoiding a-trous filter) in front of ptRenderSampleBuffer, and frame
+ * statistics (luminance histogram, automatic exposure, a noise estimate from
+ * two half renders).
  *
  * Conventions: creators return NULL on failure and set ptGetLastError();
  * other calls return 0 on success or a non-zero status (HIP / RCCL error
@@ -102,7 +104,8 @@ enum {
     PT_KERNEL_ROUNDS  = 6,   /* a round batch: several rounds of every tile in one launch */
     PT_KERNEL_DENOISE = 7,   /* one a-trous iteration of ptDenoiseSampleBuffer */
     PT_KERNEL_GUIDES  = 8,   /* ptRenderDenoiseGuides */
-    PT_KERNEL_COUNT   = 9,
+    PT_KERNEL_STATS   = 9,   /* ptComputeFrameStatistics' pass and ptAccumulateSampleBuffer's add */
+    PT_KERNEL_COUNT   = 10,
 };
 
 /* resolve_parameters (src/integrator/integrator.hpp:12-48). */
@@ -410,6 +413,34 @@ enum {
     PT_DENOISE_VARIANT_LATTICE = 2,
 };
 int  ptSetDenoiseVariant(pt_denoise_guides* guides, uint32_t variant);
+
+/* Frame statistics (no reference counterpart; definition, kernel design and
+ * measured times in DESIGN.md §6 row 6; helpers that read the result in
+ * pt_stats.h): one device pass over sample buffer a, or over a and b, two
+ * independent renders of one frame (renderers whose FrameIndex differ by
+ * 1 << 24).  With b the luminance part of *out describes a + b, the combined
+ * frame, and the noise part the relative half-difference of the pixels
+ * filled in both; without b the noise fields are 0.  Neither buffer is
+ * written.  Blocks, like ptReadSampleBuffer.  The result holds counts and
+ * min/max only and equals ptsFrameStatistics' (pt_scene.h) bit for bit.
+ * Fails, launching nothing and leaving *out untouched, on a NULL device, a or
+ * out, on b == a, and on a or b of another device or b of another size. */
+int  ptComputeFrameStatistics(pt_device* device, pt_sample_buffer* a, pt_sample_buffer* b,
+                              pt_frame_statistics* out);
+/* Enqueues dst's accumulator += src's, each component in binary32: combines
+ * two halves without a host round trip.  src is not written.  Fails,
+ * launching nothing, on a NULL argument, dst == src, or buffers of different
+ * size or of another device. */
+int  ptAccumulateSampleBuffer(pt_device* device, pt_sample_buffer* dst, pt_sample_buffer* src);
+/* The statistics kernel's histogram update (no effect on results): PLAIN =
+ * one LDS atomic per lane, UNIFORM = one per wave when all of its active
+ * lanes share a bin, AUTO = the one kept after measuring. */
+enum {
+    PT_STATS_VARIANT_AUTO    = 0,
+    PT_STATS_VARIANT_PLAIN   = 1,
+    PT_STATS_VARIANT_UNIFORM = 2,
+};
+int  ptSetFrameStatisticsVariant(pt_device* device, uint32_t variant);
 
 /* Bit-exact Trace() (scene.glsl.inc:522-611) of n rays: origins (3n floats),
  * packed unit velocities (n), durations (n) -> n hit records. */

@@ -213,8 +213,31 @@ typedef struct pt_denoise_parameters {
     float    SigmaAlbedo;              /* > 0 */
 } pt_denoise_parameters;
 
+/* Frame statistics (no reference counterpart; definition in DESIGN.md §6 row
+ * 6, arithmetic in pt_stats.h): integer counts and float min/max of one
+ * accumulator, or of the sum A + B of two with the noise fields taken from
+ * the pair.  Computed by ptComputeFrameStatistics (pt_api.h) and
+ * ptsFrameStatistics (pt_scene.h), bit for bit alike.
+ * filled + empty + nonfinite = pixels; dark pixels are filled ones. */
+#define PT_STATS_BINS 256
+
+typedef struct pt_frame_statistics {
+    uint64_t pixels;                   /* width * height */
+    uint64_t filled;                   /* all four components finite, w > 0 */
+    uint64_t empty;                    /* all finite, w <= 0 */
+    uint64_t nonfinite;                /* a NaN or an infinity in any component */
+    uint64_t dark;                     /* filled with Y = y / w <= 0: counted, not binned */
+    uint32_t luminance_histogram[PT_STATS_BINS];   /* pt_stats_bin(Y) of filled pixels with Y > 0 */
+    float    min_luminance, max_luminance;         /* over filled pixels with Y > 0; 0, 0 without any */
+    float    min_samples, max_samples;             /* w over filled pixels; 0, 0 without any */
+    uint64_t noise_pixels;             /* pair: filled in A and in B, Y_A + Y_B > 0, r finite */
+    uint64_t noise_skipped;            /* pair: filled in A and in B, not counted above */
+    uint32_t noise_histogram[PT_STATS_BINS];       /* pt_stats_bin(r), r = |Y_A - Y_B| / (Y_A + Y_B) */
+} pt_frame_statistics;
+
 #ifdef __cplusplus
 }
+static_assert(sizeof(pt_frame_statistics) == 2120, "frame_statistics");
 static_assert(sizeof(pt_denoise_guide) == 32, "denoise_guide");
 static_assert(sizeof(pt_denoise_parameters) == 20, "denoise_parameters");
 static_assert(sizeof(pt_packed_transform) == 128, "packed_transform");

@@ -176,6 +176,31 @@ void ptsSetSpectrumTablePath(const char* path);
 int  ptsDenoise(uint32_t width, uint32_t height, const float* accum_rgba, const pt_denoise_guide* guides,
                 const pt_denoise_parameters* params, float* out_rgba);
 
+/* Frame statistics on the host (no reference counterpart; definition in
+ * DESIGN.md §6 row 6, arithmetic in pt_stats.h): the CPU path for saved
+ * accumulators and the implementation ptComputeFrameStatistics (pt_api.h) is
+ * compared with, bit for bit.  accum_a: width*height*4 floats as
+ * ptReadSampleBuffer returns them.  accum_b NULL: the statistics of A, noise
+ * fields 0.  accum_b given (an independent render of the same frame): the
+ * luminance part describes A + B, each component added in binary32, and the
+ * noise part the pixels filled in both.  Returns non-zero, leaving *out
+ * untouched, on a NULL accum_a or out, an empty image or accum_b == accum_a.
+ * Single-threaded. */
+int  ptsFrameStatistics(uint32_t width, uint32_t height, const float* accum_a, const float* accum_b,
+                        pt_frame_statistics* out);
+/* pt_stats.h's bin function and double helpers as library calls (for callers
+ * that cannot include the header): the bin of a value; the lower edge of bin
+ * 0..256 (0 outside); the percentile bin of a 256-bin histogram (-1 when
+ * empty); its log-average between two percentiles; key / log-average of the
+ * luminance histogram (1 when empty); the upper edge of the noise histogram's
+ * percentile bin (+infinity when empty). */
+int    ptsStatsBin(float value);
+double ptsStatsBinEdge(int bin);
+int    ptsStatsPercentileBin(const uint32_t* histogram, double q);
+double ptsStatsLogAverage(const uint32_t* histogram, double q_lo, double q_hi);
+double ptsStatsAutoBrightness(const pt_frame_statistics* stats, double key, double q_lo, double q_hi);
+double ptsStatsNoise(const pt_frame_statistics* stats, double q);
+
 #ifdef __cplusplus
 }
 #endif

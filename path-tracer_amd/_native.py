@@ -88,6 +88,28 @@ class pt_denoise_parameters(C.Structure):
     ]
 
 
+STATS_BINS = 256
+
+
+class pt_frame_statistics(C.Structure):
+    """pt_frame_statistics (include/pt_packed.h)."""
+    _fields_ = [
+        ("pixels", C.c_uint64),
+        ("filled", C.c_uint64),
+        ("empty", C.c_uint64),
+        ("nonfinite", C.c_uint64),
+        ("dark", C.c_uint64),
+        ("luminance_histogram", C.c_uint32 * STATS_BINS),
+        ("min_luminance", C.c_float),
+        ("max_luminance", C.c_float),
+        ("min_samples", C.c_float),
+        ("max_samples", C.c_float),
+        ("noise_pixels", C.c_uint64),
+        ("noise_skipped", C.c_uint64),
+        ("noise_histogram", C.c_uint32 * STATS_BINS),
+    ]
+
+
 class pt_packed_transform(C.Structure):
     _fields_ = [("To", C.c_float * 16), ("From", C.c_float * 16)]
 
@@ -175,6 +197,8 @@ KERNEL_DENOISE = 7   # one a-trous iteration (PT_KERNEL_DENOISE)
 KERNEL_GUIDES = 8    # ptRenderDenoiseGuides (PT_KERNEL_GUIDES)
 DENOISE_MAX_ITERATIONS = 8
 DENOISE_VARIANT_AUTO, DENOISE_VARIANT_GATHER, DENOISE_VARIANT_LATTICE = 0, 1, 2
+KERNEL_STATS = 9     # the frame statistics pass and the sample-buffer add (PT_KERNEL_STATS)
+STATS_VARIANT_AUTO, STATS_VARIANT_PLAIN, STATS_VARIANT_UNIFORM = 0, 1, 2
 
 _vp = C.c_void_p
 _u32 = C.c_uint32
@@ -239,6 +263,13 @@ SCENE_API = {
     "ptsLoadSpectrumTable": (_i32, [C.c_char_p]),
     "ptsSetSpectrumTablePath": (None, [C.c_char_p]),
     "ptsDenoise": (_i32, [_u32, _u32, _fptr, _vp, C.POINTER(pt_denoise_parameters), _fptr]),
+    "ptsFrameStatistics": (_i32, [_u32, _u32, _fptr, _fptr, C.POINTER(pt_frame_statistics)]),
+    "ptsStatsBin": (_i32, [C.c_float]),
+    "ptsStatsBinEdge": (C.c_double, [_i32]),
+    "ptsStatsPercentileBin": (_i32, [_u32ptr, C.c_double]),
+    "ptsStatsLogAverage": (C.c_double, [_u32ptr, C.c_double, C.c_double]),
+    "ptsStatsAutoBrightness": (C.c_double, [C.POINTER(pt_frame_statistics), C.c_double, C.c_double, C.c_double]),
+    "ptsStatsNoise": (C.c_double, [C.POINTER(pt_frame_statistics), C.c_double]),
 }
 
 HIP_API = {
@@ -301,6 +332,9 @@ HIP_API = {
     "ptWriteDenoiseGuides": (_i32, [_vp, _vp, _vp]),
     "ptDenoiseSampleBuffer": (_i32, [_vp, _vp, _vp, C.POINTER(pt_denoise_parameters), _vp]),
     "ptSetDenoiseVariant": (_i32, [_vp, _u32]),
+    "ptComputeFrameStatistics": (_i32, [_vp, _vp, _vp, C.POINTER(pt_frame_statistics)]),
+    "ptAccumulateSampleBuffer": (_i32, [_vp, _vp, _vp]),
+    "ptSetFrameStatisticsVariant": (_i32, [_vp, _u32]),
     "ptCheckFastDivision": (_i32, [_vp, C.c_uint64, _u32, C.POINTER(C.c_uint64)]),
     "ptCheckFastReciprocal": (_i32, [_vp, C.POINTER(C.c_uint64)]),
     "ptExtendStats": (_i32, [_vp, _vp, C.POINTER(C.c_uint64)]),

@@ -125,6 +125,17 @@ hipError_t pt_launch_denoise(const float4* in, bool accumulator, const float4* g
                              hipStream_t st);
 // Iterations = 0: out = the accumulator's mean, .w = 1 (zeros where empty).
 hipError_t pt_launch_denoise_mean(const float4* accum, uint32_t n, float4* out, hipStream_t st);
+// Frame statistics (stats.hip) of accumulator a, or of
+// a + b with the noise fields from the pair (b != nullptr), added into *out,
+// which the caller has cleared: counts as they are, the two minima as the
+// complement of their bit patterns, pixels untouched.  uniform: the
+// one-atomic-per-wave shortcut for waves whose lanes share a bin (same
+// result).  pt_frame_statistics_grid: the blocks launched for n pixels.
+uint32_t pt_frame_statistics_grid(uint64_t n, uint32_t cu_count);
+hipError_t pt_launch_frame_statistics(const float4* a, const float4* b, uint64_t n, uint32_t cu_count, bool uniform,
+                                      pt_frame_statistics* out, hipStream_t st);
+// dst += src per component.
+hipError_t pt_launch_accumulate(float4* dst, const float4* src, uint64_t n, hipStream_t st);
 // compact: the completion-queue instantiation (ShadeTile), for scenes whose
 // paths also end at surfaces.
 hipError_t pt_launch_shade(const ptd::dscene& S, const ptd::dslots& L, const ptd::dframe& F, const ptd::dparams& P,

@@ -105,6 +105,10 @@ struct pt_device {
     hipStream_t group_stream[PT_MAX_SPLIT - 1] = {};
     hipEvent_t fork_event = nullptr;
     hipEvent_t join_event[PT_MAX_SPLIT - 1] = {};
+    // ptComputeFrameStatistics' result on the device: allocated at the first
+    // call, cleared on `stream` before every launch.
+    pt_frame_statistics* stats = nullptr;
+    uint32_t stats_variant = PT_STATS_VARIANT_AUTO;
 };
 
 struct pt_scene {
@@ -537,6 +541,7 @@ void ptDestroyDevice(pt_device* d)
         if (d->join_event[g]) (void)hipEventDestroy(d->join_event[g]);
     }
     if (d->fork_event) (void)hipEventDestroy(d->fork_event);
+    if (d->stats) (void)hipFree(d->stats);
     (void)hipStreamDestroy(d->stream);
     delete d;
 }
@@ -2194,6 +2199,78 @@ int ptDenoiseSampleBuffer(pt_device* d, pt_sample_buffer* src, pt_denoise_guides
         if (int e = EndTimed(d, ep)) return e;
         in = out;
     }
+    return 0;
+}
+
+// --- frame statistics (stats.hip) ------------------------------
+
+// Automatic mode's histogram update: the wave-uniform shortcut.  Without it a
+// constant image runs 19 % (1920x1080) to 37 % (3840x2160) slower than a
+// rendered one, far beyond the 1 - 3 % spread of repeated runs; with it the
+// constant image is the faster of the two and the rendered one keeps its
+// time within that spread.
+static bool StatsUniform(uint32_t variant)
+{
+    return variant != PT_STATS_VARIANT_PLAIN;
+}
+
+int ptSetFrameStatisticsVariant(pt_device* d, uint32_t variant)
+{
+    if (!d || variant > PT_STATS_VARIANT_UNIFORM) { SetError("bad frame statistics variant"); return -1; }
+    d->stats_variant = variant;
+    return 0;
+}
+
+int ptComputeFrameStatistics(pt_device* d, pt_sample_buffer* a, pt_sample_buffer* b, pt_frame_statistics* out)
+{
+    if (!d || !a || !out) { SetError("null argument"); return -1; }
+    if (b == a) { SetError("frame statistics: a and b are the same sample buffer"); return -1; }
+    if (a->dev != d || (b && b->dev != d)) { SetError("frame statistics: sample buffer of another device"); return -1; }
+    if (b && (b->width != a->width || b->height != a->height)) {
+        SetError("frame statistics: size mismatch (a %ux%u, b %ux%u)", a->width, a->height, b->width, b->height);
+        return -1;
+    }
+    PT_HIP(hipSetDevice(d->id));
+    if (!d->stats) {
+        if (hipError_t e = hipMalloc(&d->stats, sizeof(pt_frame_statistics)); e != hipSuccess) {
+            d->stats = nullptr;
+            SetError("frame statistics allocation failed: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+    }
+    const uint64_t n = (uint64_t)a->width * a->height;
+    PT_HIP(hipMemsetAsync(d->stats, 0, sizeof(pt_frame_statistics), d->stream));
+    event_pair ep{};
+    if (int e = BeginTimed(d, PT_KERNEL_STATS, ep)) return e;
+    PT_HIP(pt_launch_frame_statistics(a->accum, b ? b->accum : nullptr, n, d->cu_count, StatsUniform(d->stats_variant),
+                                      d->stats, d->stream));
+    if (int e = EndTimed(d, ep)) return e;
+    pt_frame_statistics s;
+    PT_HIP(hipMemcpyAsync(&s, d->stats, sizeof(s), hipMemcpyDeviceToHost, d->stream));
+    PT_WAIT(d);
+    // The kernel keeps each minimum as the complement of its bit pattern, so
+    // that 0 is "no value" for all four fields.
+    s.pixels = n;
+    s.min_luminance = pt_f2u(s.max_luminance) ? pt_u2f(~pt_f2u(s.min_luminance)) : 0.0f;
+    s.min_samples = pt_f2u(s.max_samples) ? pt_u2f(~pt_f2u(s.min_samples)) : 0.0f;
+    *out = s;
+    return 0;
+}
+
+int ptAccumulateSampleBuffer(pt_device* d, pt_sample_buffer* dst, pt_sample_buffer* src)
+{
+    if (!d || !dst || !src) { SetError("null argument"); return -1; }
+    if (dst == src) { SetError("accumulate: dst and src are the same sample buffer"); return -1; }
+    if (dst->dev != d || src->dev != d) { SetError("accumulate: sample buffer of another device"); return -1; }
+    if (dst->width != src->width || dst->height != src->height) {
+        SetError("accumulate: size mismatch (dst %ux%u, src %ux%u)", dst->width, dst->height, src->width, src->height);
+        return -1;
+    }
+    PT_HIP(hipSetDevice(d->id));
+    event_pair ep{};
+    if (int e = BeginTimed(d, PT_KERNEL_STATS, ep)) return e;
+    PT_HIP(pt_launch_accumulate(dst->accum, src->accum, (uint64_t)dst->width * dst->height, d->stream));
+    if (int e = EndTimed(d, ep)) return e;
     return 0;
 }
 

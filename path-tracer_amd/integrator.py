@@ -73,6 +73,11 @@ class Device:
     def reset_kernel_stats(self):
         _check(N.hip_lib().ptResetKernelStats(self._h), "ptResetKernelStats")
 
+    def set_statistics_variant(self, variant: int):
+        """STATS_VARIANT_AUTO / _PLAIN / _UNIFORM: the statistics kernel's
+        histogram update (identical results; ptSetFrameStatisticsVariant)."""
+        _check(N.hip_lib().ptSetFrameStatisticsVariant(self._h, int(variant)), "ptSetFrameStatisticsVariant")
+
     def check_fast_division(self, n: int, seed: int = 1) -> int:
         m = C.c_uint64(0)
         _check(N.hip_lib().ptCheckFastDivision(self._h, n, seed, C.byref(m)), "ptCheckFastDivision")
@@ -172,6 +177,141 @@ class ResolveParameters:
 
     def as_struct(self) -> N.pt_resolve_parameters:
         return N.pt_resolve_parameters(self.Brightness, self.ToneMappingMode, self.ToneMappingWhiteLevel)
+
+    @classmethod
+    def auto(cls, stats: "FrameStatistics", key: float = 0.18, q_lo: float = 0.01, q_hi: float = 0.99,
+             **kw) -> "ResolveParameters":
+        """Resolve parameters whose Brightness puts the frame's log-average
+        luminance at `key` (FrameStatistics.auto_brightness); **kw are the
+        other fields, e.g. ToneMappingMode."""
+        return cls(Brightness=stats.auto_brightness(key, q_lo, q_hi), **kw)
+
+
+class FrameStatistics:
+    """pt_frame_statistics (pt_packed.h): pixel classes,
+    a 256-bin quarter-octave luminance histogram, luminance and sample-count
+    range and, from a pair of half renders, the histogram of the relative
+    half-difference r = |Y_A - Y_B| / (Y_A + Y_B).  Every field is an
+    attribute (the histograms as uint32 arrays); the methods are pt_stats.h's
+    double helpers, evaluated by libptscene.so."""
+
+    _COUNTS = ("pixels", "filled", "empty", "nonfinite", "dark", "noise_pixels", "noise_skipped")
+    _FLOATS = ("min_luminance", "max_luminance", "min_samples", "max_samples")
+    _HISTOGRAMS = ("luminance_histogram", "noise_histogram")
+
+    def __init__(self, struct: N.pt_frame_statistics):
+        self._s = struct
+        for f in self._COUNTS:
+            setattr(self, f, int(getattr(struct, f)))
+        for f in self._FLOATS:
+            setattr(self, f, np.float32(getattr(struct, f)))
+        for f in self._HISTOGRAMS:
+            setattr(self, f, np.ctypeslib.as_array(getattr(struct, f)).astype(np.uint32))
+
+    def as_struct(self) -> N.pt_frame_statistics:
+        return self._s
+
+    def tobytes(self) -> bytes:
+        return bytes(self._s)
+
+    def _histogram(self, which: str):
+        return self._s.noise_histogram if which == "noise" else self._s.luminance_histogram
+
+    def percentile(self, q: float, which: str = "luminance") -> int:
+        """The smallest bin whose cumulative count reaches ceil(q * total) of
+        the luminance (or "noise") histogram; -1 when it is empty."""
+        return int(N.scene_lib().ptsStatsPercentileBin(self._histogram(which), float(q)))
+
+    def log_average(self, q_lo: float = 0.01, q_hi: float = 0.99, which: str = "luminance") -> float:
+        """Geometric mean of the bin centres between two percentile bins (0 when empty)."""
+        return float(N.scene_lib().ptsStatsLogAverage(self._histogram(which), float(q_lo), float(q_hi)))
+
+    def auto_brightness(self, key: float = 0.18, q_lo: float = 0.01, q_hi: float = 0.99) -> float:
+        """key / log_average: ResolveParameters.Brightness is a linear scale
+        in front of the tone curve.  1 for a frame without a binned pixel."""
+        return float(N.scene_lib().ptsStatsAutoBrightness(C.byref(self._s), float(key), float(q_lo), float(q_hi)))
+
+    def noise(self, q: float = 0.95) -> float:
+        """An upper bound of the relative noise of a share q of the pair
+        pixels: the upper edge of the noise histogram's percentile bin
+        (inf without a pair pixel)."""
+        return float(N.scene_lib().ptsStatsNoise(C.byref(self._s), float(q)))
+
+    @staticmethod
+    def bin_edges() -> np.ndarray:
+        """The 257 bin edges (float64): bin b is [edges[b], edges[b + 1])."""
+        L = N.scene_lib()
+        return np.array([L.ptsStatsBinEdge(b) for b in range(N.STATS_BINS + 1)], dtype=np.float64)
+
+    def __eq__(self, other):
+        return isinstance(other, FrameStatistics) and self.tobytes() == other.tobytes()
+
+    def __repr__(self):
+        return (f"FrameStatistics(pixels={self.pixels}, filled={self.filled}, empty={self.empty}, "
+                f"nonfinite={self.nonfinite}, dark={self.dark}, luminance=[{self.min_luminance}, "
+                f"{self.max_luminance}], samples=[{self.min_samples}, {self.max_samples}], "
+                f"noise_pixels={self.noise_pixels}, noise_skipped={self.noise_skipped})")
+
+
+def _accumulator(a, what="accumulator") -> np.ndarray:
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4 or a.size == 0:
+        raise ValueError(f"{what} of shape {a.shape}, expected (H, W, 4)")
+    return a
+
+
+def frame_statistics_host(accum: np.ndarray, other: "np.ndarray | None" = None) -> FrameStatistics:
+    """The frame statistics on the CPU (ptsFrameStatistics, libptscene.so):
+    for saved accumulators on a machine without a GPU, and the implementation
+    SampleBuffer.statistics equals bit for bit.  accum, other: (H, W, 4) XYZ
+    sums + sample count; with `other`, an independent render of the same
+    frame, the luminance part describes accum + other and the noise part the
+    pair."""
+    a = _accumulator(accum)
+    b = None
+    if other is not None:
+        b = _accumulator(other, "second accumulator")
+        if b.shape != a.shape:
+            raise ValueError(f"accumulators of shapes {a.shape} and {b.shape}")
+    out = N.pt_frame_statistics()
+    rc = N.scene_lib().ptsFrameStatistics(a.shape[1], a.shape[0], N.fptr(a), N.fptr(b) if b is not None else None,
+                                          C.byref(out))
+    if rc != 0:
+        raise PathTracerError(f"ptsFrameStatistics: bad arguments (status {rc})")
+    return FrameStatistics(out)
+
+
+def render_until_noise(renderer_a: "BasicRenderer", renderer_b: "BasicRenderer", threshold: float, q: float = 0.95,
+                       check_every: int = 8, min_pair_fraction: float = 0.99, max_rounds: int = 1024):
+    """Render one frame as two independent halves until it is converged:
+    renderer_b.FrameIndex := renderer_a.FrameIndex + (1 << 24) (the stream
+    offset), both are Reset, run Run(2) and then Run(1) rounds in lockstep;
+    every `check_every` rounds the pair statistics of their two sample
+    buffers are computed (sa.statistics(sb)), and the loop ends when at least
+    `min_pair_fraction` of the pixels are filled in both halves and
+    noise(q) <= threshold, or after `max_rounds` rounds.  The renderers are on
+    one device, on sample buffers of one size that the caller has left empty
+    (new ones are); RenderFlags should include ACCUMULATE.  Returns (rounds
+    per half, the last FrameStatistics); sa.accumulate(sb) then makes sa the
+    combined frame those statistics describe."""
+    if check_every < 1 or max_rounds < 2:
+        raise ValueError("check_every >= 1 and max_rounds >= 2 are required")
+    sa, sb = renderer_a.sample_buffer, renderer_b.sample_buffer
+    renderer_b.FrameIndex = renderer_a.FrameIndex + (1 << 24)
+    for r in (renderer_a, renderer_b):
+        r.reset()
+    for r in (renderer_a, renderer_b):
+        r.run(2)
+    rounds, stats = 2, None
+    while True:
+        if rounds % check_every == 0 or rounds >= max_rounds:
+            stats = sa.statistics(sb)
+            if rounds >= max_rounds or (stats.noise_pixels >= min_pair_fraction * stats.pixels and
+                                        stats.noise(q) <= threshold):
+                return rounds, stats
+        for r in (renderer_a, renderer_b):
+            r.run(1)
+        rounds += 1
 
 
 class DenoiseParameters:
@@ -301,6 +441,23 @@ class SampleBuffer:
                 dst.close()
             raise
         return dst
+
+    def statistics(self, other: "SampleBuffer | None" = None) -> FrameStatistics:
+        """Frame statistics on the device (ptComputeFrameStatistics; blocks):
+        of this buffer, or, with `other` (an independent render of the same
+        frame), of this + other with the noise histogram of the pair.
+        Neither buffer is written."""
+        out = N.pt_frame_statistics()
+        _check(N.hip_lib().ptComputeFrameStatistics(self.device.handle, self._h,
+                                                    other.handle if other is not None else None, C.byref(out)),
+               "ptComputeFrameStatistics")
+        return FrameStatistics(out)
+
+    def accumulate(self, src: "SampleBuffer"):
+        """This accumulator += src's, per component in float32, on the device
+        (ptAccumulateSampleBuffer; enqueues).  src is not written."""
+        _check(N.hip_lib().ptAccumulateSampleBuffer(self.device.handle, self._h, src.handle),
+               "ptAccumulateSampleBuffer")
 
     def read_resolved(self) -> np.ndarray:
         """OutColor of the last render(): (H, W, 4) float32, alpha 1."""

@@ -14,11 +14,16 @@
   iteration (step 1 .. 32) of the gather and the lattice kernel and of the
   automatic choice, ms per 5-iteration call, and the guide kernel, on C3 at
   1920x1080 and 3840x2160.
+* stats (ptComputeFrameStatistics, stats.hip): kernel ms
+  of the statistics pass, single and pair, with and without the wave-uniform
+  shortcut, on C3's accumulator after 8 rounds and on a constant image, with
+  ptRenderSampleBuffer and ptAccumulateSampleBuffer on the same buffers, at
+  1920x1080 and 3840x2160; every figure three times, to show the spread.
 * host builds (§8(f) row 3): mesh BVH build of a 1.96 M-face mesh on 1 and
   on all of the job's threads, and the RGB -> spectrum table.
 
 Kernel times are HIP events on the device stream (ptGetKernelStats).
-Prints one JSON object.  usage: bench_next.py [resolve|denoise|preview|openpbr|host ...]
+Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|preview|openpbr|host ...]
 (default: all).
 """
 import json
@@ -37,6 +42,7 @@ from exp_reorder import load  # noqa: E402
 HBM_GBPS = 8000.0
 K_RESOLVE, K_PREVIEW, K_EXTEND, K_SHADE, K_ROUND = 3, 4, 1, 2, 5
 K_DENOISE, K_GUIDES = 7, 8
+K_STATS = 9
 
 
 def timed(dev, kernel, fn, reps):
@@ -111,6 +117,56 @@ def denoise(pt, dev):
             res[f"{name}_step_ms"] = {str(1 << (k - 1)): round(total[k] - total[k - 1], 4) for k in range(1, 7)}
         out[f"{W}x{H}"] = res
         for x in (guides, r, dst, sb):
+            x.close()
+    ds.close()
+    return out
+
+
+def stats(pt, dev):
+    """Per size, {image}_{single|pair}_{plain|uniform}_ms: the statistics
+    kernel on the rendered halves (C3, 8 rounds each, FrameIndex 0 and
+    1 << 24) and on constant images; {image}_resolve_ms and accumulate_ms:
+    the yardsticks on the same buffers.  Each value is a list: the mean of 10
+    timed calls after a warm-up call, taken three times in turn."""
+    out = {}
+    scene = pt.Scene.config(3)
+    ds = pt.DeviceScene(dev)
+    ds.update(scene)
+    variants = {"plain": pt.STATS_VARIANT_PLAIN, "uniform": pt.STATS_VARIANT_UNIFORM}
+    for W, H in ((1920, 1080), (3840, 2160)):
+        halves = [pt.SampleBuffer(dev, W, H), pt.SampleBuffer(dev, W, H)]
+        for sb, frame in zip(halves, (0, 1 << 24)):
+            r = pt.BasicRenderer(dev, ds, sb)
+            r.RenderFlags = 3
+            r.FrameIndex = frame
+            r.reset()
+            r.run(8)
+            dev.synchronize()
+            r.close()
+        flat = [pt.SampleBuffer(dev, W, H), pt.SampleBuffer(dev, W, H), pt.SampleBuffer(dev, W, H)]
+        for sb, value in zip(flat, ((4.0, 2.0, 1.0, 8.0), (6.0, 3.0, 1.5, 8.0), (0.0, 0.0, 0.0, 0.0))):
+            sb.write(np.broadcast_to(np.array(value, np.float32), (H, W, 4)).copy())
+        images = {"rendered": halves, "constant": flat[:2]}
+        res = {"pixels": W * H, "rendered_filled": halves[0].statistics().filled}
+        runs = {}
+        for name, (a, b) in images.items():
+            runs[f"{name}_resolve_ms"] = (K_RESOLVE, lambda a=a: a.render(ToneMappingMode=pt.TONE_MAPPING_ACES))
+            for vname, variant in variants.items():
+                runs[f"{name}_single_{vname}_ms"] = (K_STATS, lambda a=a, v=variant: (dev.set_statistics_variant(v),
+                                                                                       a.statistics()))
+                runs[f"{name}_pair_{vname}_ms"] = (K_STATS, lambda a=a, b=b, v=variant: (dev.set_statistics_variant(v),
+                                                                                         a.statistics(b)))
+        runs["accumulate_ms"] = (K_STATS, lambda: flat[2].accumulate(flat[0]))
+        for key in runs:
+            res[key] = []
+        for _ in range(3):
+            for key, (kernel, fn) in runs.items():
+                fn()   # warm
+                ms, _ = timed(dev, kernel, fn, 10)
+                res[key].append(round(ms, 4))
+        dev.set_statistics_variant(pt.STATS_VARIANT_AUTO)
+        out[f"{W}x{H}"] = res
+        for x in halves + flat:
             x.close()
     ds.close()
     return out
@@ -195,7 +251,7 @@ def host_builds(pt):
 
 def main():
     pt = load()
-    entries = {"resolve": resolve, "denoise": denoise, "preview": preview, "openpbr": openpbr}
+    entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "preview": preview, "openpbr": openpbr}
     want = sys.argv[1:] or list(entries) + ["host"]
     dev = pt.Device(0)
     res = {name: fn(pt, dev) for name, fn in entries.items() if name in want}

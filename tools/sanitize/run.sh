@@ -37,6 +37,7 @@ run asan_models "$A" model $(ls -d "$C"/models/m*/ | while read d; do ls "$d"*.o
 run asan_scenes "$A" scene $(ls -d "$C"/scenes/s*/ | sed 's|$|scene.json|') "$C/scenes/src/scene.json"
 run asan_render "$A" render
 run asan_denoise "$A" denoise
+run asan_stats "$A" stats
 PT_BVH_THREADS=8 run tsan_bvh "$T" bvh 300000
 run tsan_render "$T" render
 PT_BVH_THREADS=8 run asan_bvh "$A" bvh 200000

@@ -17,6 +17,10 @@
 //   san_driver denoise          ptsDenoise on random small images: sizes below
 //                               the 2 * step halo, every iteration count, an
 //                               all-empty image, rejected arguments
+//   san_driver stats            ptsFrameStatistics and the ptsStats* helpers on
+//                               small random, empty and NaN / inf / denormal
+//                               images, single and pair, one pixel included;
+//                               rejected arguments
 #include "../../path-tracer_amd/csrc/scene/scene.hpp"
 #include "../../path-tracer_amd/csrc/scene/configs.hpp"
 #include "../../path-tracer_amd/csrc/scene/image.hpp"
@@ -213,9 +217,67 @@ static int Denoise()
     return bad != 0;
 }
 
+static int Stats()
+{
+    std::mt19937 rng(12);
+    std::uniform_real_distribution<float> u(0.0f, 4.0f);
+    const float nan = std::nanf(""), inf = HUGE_VALF;
+    const float odd[] = {0.0f, -0.0f, -1.0f, nan, inf, -inf, 1e-45f, 1e-38f, 3e38f, 1.0f, 4294967296.0f, 2.3283064e-10f};
+    const uint32_t sizes[][2] = {{1, 1}, {1, 7}, {3, 2}, {16, 16}, {17, 33}, {40, 24}, {67, 45}};
+    int bad = 0;
+    for (auto& wh : sizes) {
+        const uint32_t W = wh[0], H = wh[1];
+        const size_t n = (size_t)W * H;
+        // kind 0: random; 1: all empty; 2: every component drawn from the odd values (NaN, inf, denormals ...)
+        for (int kind = 0; kind < 3; kind++) {
+            std::vector<float> a(4 * n), b(4 * n);
+            for (std::vector<float>* v : {&a, &b}) {
+                for (size_t i = 0; i < 4 * n; i++) {
+                    if (kind == 0) (*v)[i] = i % 4 == 3 ? (float)(rng() % 5) : u(rng);
+                    else if (kind == 1) (*v)[i] = 0.0f;
+                    else (*v)[i] = odd[rng() % (sizeof(odd) / sizeof(odd[0]))];
+                }
+            }
+            for (int pair = 0; pair < 2; pair++) {
+                pt_frame_statistics s;
+                if (ptsFrameStatistics(W, H, a.data(), pair ? b.data() : nullptr, &s) != 0) { std::printf("stats: failed\n"); return 1; }
+                uint64_t lum = 0, noise = 0;
+                for (int k = 0; k < PT_STATS_BINS; k++) { lum += s.luminance_histogram[k]; noise += s.noise_histogram[k]; }
+                bad += s.pixels != n || s.filled + s.empty + s.nonfinite != n || lum + s.dark != s.filled ||
+                       noise != s.noise_pixels || (!pair && (s.noise_pixels || s.noise_skipped));
+                std::printf("stats %ux%u kind %d pair %d: filled %llu empty %llu nonfinite %llu dark %llu noise %llu + %llu, "
+                            "brightness %g noise %g\n", W, H, kind, pair, (unsigned long long)s.filled,
+                            (unsigned long long)s.empty, (unsigned long long)s.nonfinite, (unsigned long long)s.dark,
+                            (unsigned long long)s.noise_pixels, (unsigned long long)s.noise_skipped,
+                            ptsStatsAutoBrightness(&s, 0.18, 0.01, 0.99), ptsStatsNoise(&s, 0.95));
+                for (double q : {1e-12, 0.5, 1.0}) {
+                    const int p = ptsStatsPercentileBin(s.luminance_histogram, q);
+                    bad += p < -1 || p > 255 || (lum == 0) != (p == -1);
+                    (void)ptsStatsLogAverage(s.luminance_histogram, q, 1.0);
+                }
+            }
+        }
+    }
+    // rejected arguments leave `out` untouched
+    float acc[4] = {1, 1, 1, 1};
+    pt_frame_statistics out;
+    std::memset(&out, 0x55, sizeof(out));
+    const pt_frame_statistics before = out;
+    bad += ptsFrameStatistics(1, 1, nullptr, nullptr, &out) == 0;
+    bad += ptsFrameStatistics(1, 1, acc, nullptr, nullptr) == 0;
+    bad += ptsFrameStatistics(0, 1, acc, nullptr, &out) == 0;
+    bad += ptsFrameStatistics(1, 0, acc, nullptr, &out) == 0;
+    bad += ptsFrameStatistics(1, 1, acc, acc, &out) == 0;
+    bad += std::memcmp(&out, &before, sizeof(out)) != 0;
+    bad += ptsStatsPercentileBin(nullptr, 0.5) != -1 || ptsStatsBinEdge(-1) != 0.0 || ptsStatsBinEdge(257) != 0.0;
+    for (float v : odd) bad += ptsStatsBin(v) < 0 || ptsStatsBin(v) > 255;
+    std::printf("stats: %d checks wrong\n", bad);
+    return bad != 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise ...\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise|stats ...\n"); return 2; }
     std::string cmd = argv[1];
     if (cmd == "decode") return Decode(argc - 2, argv + 2);
     if (cmd == "model") return Model(argc - 2, argv + 2);
@@ -223,6 +285,7 @@ int main(int argc, char** argv)
     if (cmd == "render") return Render();
     if (cmd == "bvh") return Bvh(argc > 2 ? (uint32_t)std::strtoul(argv[2], nullptr, 10) : 200000u);
     if (cmd == "denoise") return Denoise();
+    if (cmd == "stats") return Stats();
     std::fprintf(stderr, "unknown command %s\n", cmd.c_str());
     return 2;
 }
