@@ -28,9 +28,10 @@
  * synchronisation, a bit-exact ray query (ptTraceRays), slot-state readback,
  * per-kernel timing, pixel-band partitioning, an RCCL frame-end reduce for
  * one-process-per-GPU rendering, a denoiser (guide images + an
- * edge-avoiding a-trous filter) in front of ptRenderSampleBuffer, and frame
+ * edge-avoiding a-trous filter) in front of ptRenderSampleBuffer, frame
  * statistics (luminance histogram, automatic exposure, a noise estimate from
- * two half renders).
+ * two half renders), and a variance-guided form of the denoiser that takes
+ * those two half renders (ptDenoiseSampleBufferPair).
  *
  * Conventions: creators return NULL on failure and set ptGetLastError();
  * other calls return 0 on success or a non-zero status (HIP / RCCL error
@@ -413,6 +414,24 @@ enum {
     PT_DENOISE_VARIANT_LATTICE = 2,
 };
 int  ptSetDenoiseVariant(pt_denoise_guides* guides, uint32_t variant);
+/* The variance-guided filter over two half renders (SVGF's spatial part,
+ * Schied et al. 2017; definition in DESIGN.md §6 row 7): a and b are two
+ * independent renders of one frame (renderers whose FrameIndex differ by
+ * 1 << 24, as for ptComputeFrameStatistics).  The filter works on a + b; its
+ * luminance edge-stop is SigmaLuminance standard deviations of the pixel's
+ * luminance, estimated from a - b, prefiltered 3x3 and filtered along with
+ * the colour, so it stops smoothing where the render has converged and does
+ * not depend on the frame's brightness.  Enqueues like ptDenoiseSampleBuffer
+ * and leaves dst in the same form; a and b are not written.  One prepare
+ * launch plus one per iteration, all counted under PT_KERNEL_DENOISE, between
+ * dst and the guides object's intermediate image (needed from Iterations >=
+ * 1); honours ptSetDenoiseVariant; two calls on the same inputs give the same
+ * bits, and the result equals ptsDenoisePair's (pt_scene.h) bit for bit.
+ * Fails, launching and writing nothing, on a NULL argument, when two of a, b
+ * and dst are the same buffer, when a, b, dst and guides differ in size or
+ * device, when Iterations > 8 or when a sigma is not > 0. */
+int  ptDenoiseSampleBufferPair(pt_device* device, pt_sample_buffer* a, pt_sample_buffer* b, pt_denoise_guides* guides,
+                               const pt_denoise_pair_parameters* params, pt_sample_buffer* dst);
 
 /* Frame statistics (no reference counterpart; definition, kernel design and
  * measured times in DESIGN.md §6 row 6; helpers that read the result in

@@ -213,6 +213,15 @@ typedef struct pt_denoise_parameters {
     float    SigmaAlbedo;              /* > 0 */
 } pt_denoise_parameters;
 
+/* The variance-guided filter over two half renders. */
+typedef struct pt_denoise_pair_parameters {
+    uint32_t Iterations;               /* 0..8, default 5: steps 1, 2, 4, 8, 16 */
+    float    SigmaLuminance;           /* > 0; in standard deviations of the pixel's luminance, every iteration */
+    float    SigmaNormal;              /* > 0 */
+    float    SigmaDepth;               /* > 0 */
+    float    SigmaAlbedo;              /* > 0 */
+} pt_denoise_pair_parameters;
+
 /* Frame statistics (no reference counterpart; definition in DESIGN.md §6 row
  * 6, arithmetic in pt_stats.h): integer counts and float min/max of one
  * accumulator, or of the sum A + B of two with the noise fields taken from
@@ -240,6 +249,7 @@ typedef struct pt_frame_statistics {
 static_assert(sizeof(pt_frame_statistics) == 2120, "frame_statistics");
 static_assert(sizeof(pt_denoise_guide) == 32, "denoise_guide");
 static_assert(sizeof(pt_denoise_parameters) == 20, "denoise_parameters");
+static_assert(sizeof(pt_denoise_pair_parameters) == 20, "denoise_pair_parameters");
 static_assert(sizeof(pt_packed_transform) == 128, "packed_transform");
 static_assert(sizeof(pt_packed_texture) == 32, "packed_texture");
 static_assert(sizeof(pt_packed_shape) == 144, "packed_shape");

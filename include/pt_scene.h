@@ -175,6 +175,18 @@ void ptsSetSpectrumTablePath(const char* path);
  * image, Iterations > 8 or a sigma that is not > 0.  Single-threaded. */
 int  ptsDenoise(uint32_t width, uint32_t height, const float* accum_rgba, const pt_denoise_guide* guides,
                 const pt_denoise_parameters* params, float* out_rgba);
+/* The variance-guided filter over two half renders on the host (definition in
+ * DESIGN.md §6 row 7): the CPU path and the implementation
+ * ptDenoiseSampleBufferPair (pt_api.h) is compared with, bit for bit.
+ * accum_a, accum_b: two independent renders of one frame (renderers whose
+ * FrameIndex differ by 1 << 24), as ptReadSampleBuffer returns them; the
+ * filter works on A + B, its luminance edge-stop scaled by the standard
+ * deviation estimated from A - B.  out_rgba as for ptsDenoise.  Returns
+ * non-zero, leaving out_rgba untouched, on a NULL argument, an empty image,
+ * accum_a == accum_b, Iterations > 8 or a sigma that is not > 0.
+ * Single-threaded. */
+int  ptsDenoisePair(uint32_t width, uint32_t height, const float* accum_a, const float* accum_b,
+                    const pt_denoise_guide* guides, const pt_denoise_pair_parameters* params, float* out_rgba);
 
 /* Frame statistics on the host (no reference counterpart; definition in
  * DESIGN.md §6 row 6, arithmetic in pt_stats.h): the CPU path for saved

@@ -17,7 +17,7 @@ from .integrator import (Device, DeviceScene, SampleBuffer, BasicRenderer, Comm,
                          DestroyBasicRenderer, DestroySampleBuffer, RenderSampleBuffer, PreviewParameters,
                          PreviewRenderContext, CreatePreviewRenderContext, RenderPreview, RetrievePreviewQueryResult,
                          DenoiseParameters, DenoiseGuides, denoise_host, FrameStatistics, frame_statistics_host,
-                         render_until_noise)
+                         render_until_noise, DenoisePairParameters, denoise_pair_host)
 from ._native import (PREVIEW_RENDER_MODE_BASE_COLOR, PREVIEW_RENDER_MODE_BASE_COLOR_SHADED, PREVIEW_RENDER_MODE_NORMAL,
                       PREVIEW_RENDER_MODE_MATERIAL_INDEX, PREVIEW_RENDER_MODE_PRIMITIVE_INDEX,
                       PREVIEW_RENDER_MODE_MESH_COMPLEXITY, PREVIEW_RENDER_MODE_SCENE_COMPLEXITY)

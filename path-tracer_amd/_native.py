@@ -88,6 +88,17 @@ class pt_denoise_parameters(C.Structure):
     ]
 
 
+class pt_denoise_pair_parameters(C.Structure):
+    """pt_denoise_pair_parameters (include/pt_packed.h)."""
+    _fields_ = [
+        ("Iterations", C.c_uint32),
+        ("SigmaLuminance", C.c_float),
+        ("SigmaNormal", C.c_float),
+        ("SigmaDepth", C.c_float),
+        ("SigmaAlbedo", C.c_float),
+    ]
+
+
 STATS_BINS = 256
 
 
@@ -263,6 +274,7 @@ SCENE_API = {
     "ptsLoadSpectrumTable": (_i32, [C.c_char_p]),
     "ptsSetSpectrumTablePath": (None, [C.c_char_p]),
     "ptsDenoise": (_i32, [_u32, _u32, _fptr, _vp, C.POINTER(pt_denoise_parameters), _fptr]),
+    "ptsDenoisePair": (_i32, [_u32, _u32, _fptr, _fptr, _vp, C.POINTER(pt_denoise_pair_parameters), _fptr]),
     "ptsFrameStatistics": (_i32, [_u32, _u32, _fptr, _fptr, C.POINTER(pt_frame_statistics)]),
     "ptsStatsBin": (_i32, [C.c_float]),
     "ptsStatsBinEdge": (C.c_double, [_i32]),
@@ -332,6 +344,7 @@ HIP_API = {
     "ptWriteDenoiseGuides": (_i32, [_vp, _vp, _vp]),
     "ptDenoiseSampleBuffer": (_i32, [_vp, _vp, _vp, C.POINTER(pt_denoise_parameters), _vp]),
     "ptSetDenoiseVariant": (_i32, [_vp, _u32]),
+    "ptDenoiseSampleBufferPair": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(pt_denoise_pair_parameters), _vp]),
     "ptComputeFrameStatistics": (_i32, [_vp, _vp, _vp, C.POINTER(pt_frame_statistics)]),
     "ptAccumulateSampleBuffer": (_i32, [_vp, _vp, _vp]),
     "ptSetFrameStatisticsVariant": (_i32, [_vp, _u32]),

@@ -19,6 +19,10 @@
 //            step lattice (x = rx, y = ry mod step), so its taps fall in a
 //            20x20 lattice window whatever the step is; the window is staged
 //            in LDS once (400 x 48 B) and the 25 taps read LDS.
+//
+// Pair filter: the same two variants over a working
+// image {colour, luminance variance}, behind one prepare launch that forms
+// the combined frame of two half renders and its prefiltered variance.
 #include "pt_device.hpp"
 #include "traverse.hpp"
 #include "kernels.hpp"
@@ -142,12 +146,20 @@ __global__ __launch_bounds__(256) void guides_kernel(dscene S, guide_args P, uin
 
 // --- filter ---------------------------------------------------------------------
 
-struct denoise_args {
+// The geometry of one iteration, shared by the single-buffer and the pair filter.
+struct filter_grid {
     uint32_t w, h;
     uint32_t step;
-    pt_denoise_sigmas sg;
     // lattice variant: residue classes and 16x16 lattice tiles per class
     uint32_t ncx, ncy;
+};
+
+struct denoise_args : filter_grid {
+    pt_denoise_sigmas sg;
+};
+
+struct pair_args : filter_grid {
+    pt_denoise_pair_sigmas sg;
 };
 
 // FIRST: the input is the accumulator (XYZ sums, sample count); the filter's
@@ -223,39 +235,66 @@ __global__ __launch_bounds__(256) void denoise_gather_kernel(const float4* __res
 constexpr uint32_t DN_WIN = 20;
 constexpr uint32_t DN_ROW = 32;
 
+// The block of the lattice variant: tile (tile_x, tile_y) of the residue
+// class (rx, ry).  Neighbouring blocks take neighbouring residues of the same
+// lattice tile: their strided window loads share cache lines.
+struct lattice_block {
+    uint32_t tile_x, tile_y, rx, ry;
+    PT_DEV explicit lattice_block(const filter_grid& P)
+    {
+        tile_x = blockIdx.x / P.ncx; rx = blockIdx.x - tile_x * P.ncx;
+        tile_y = blockIdx.y / P.ncy; ry = blockIdx.y - tile_y * P.ncy;
+    }
+    // Window record r (row-major over DN_WIN x DN_WIN): its LDS slot, and its
+    // pixel index when it lies inside the image.
+    PT_DEV bool record(const filter_grid& P, uint32_t r, uint32_t& slot, size_t& iq) const
+    {
+        const uint32_t wy = r / DN_WIN, wx = r - wy * DN_WIN;
+        slot = wy * DN_ROW + wx;
+        // lattice coordinates of the record; the window starts 2 before the tile
+        const int64_t lx = (int64_t)(tile_x * 16 + wx) - 2, ly = (int64_t)(tile_y * 16 + wy) - 2;
+        const int64_t qx = (int64_t)rx + lx * (int64_t)P.step, qy = (int64_t)ry + ly * (int64_t)P.step;
+        if (!(lx >= 0 && ly >= 0 && qx < (int64_t)P.w && qy < (int64_t)P.h)) return false;
+        iq = (size_t)qy * P.w + (size_t)qx;
+        return true;
+    }
+    // The thread's own pixel: its LDS slot, and its index when inside the image.
+    PT_DEV bool pixel(const filter_grid& P, uint32_t& slot, size_t& ip) const
+    {
+        const uint32_t tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+        slot = (ty + 2) * DN_ROW + tx + 2;
+        const uint64_t x = (uint64_t)rx + (uint64_t)(tile_x * 16 + tx) * P.step;
+        const uint64_t y = (uint64_t)ry + (uint64_t)(tile_y * 16 + ty) * P.step;
+        if (x >= P.w || y >= P.h) return false;
+        ip = (size_t)y * P.w + (size_t)x;
+        return true;
+    }
+};
+
 template <bool FIRST>
 __global__ __launch_bounds__(256) void denoise_lattice_kernel(const float4* __restrict__ in,
                                                               const float4* __restrict__ guides, denoise_args P,
                                                               float4* __restrict__ out)
 {
     __shared__ float4 sc[DN_WIN * DN_ROW], sa[DN_WIN * DN_ROW], sb[DN_WIN * DN_ROW];
-    // Neighbouring blocks take neighbouring residues of the same lattice
-    // tile: their strided window loads share cache lines.
-    const uint32_t tile_x = blockIdx.x / P.ncx, rx = blockIdx.x - tile_x * P.ncx;
-    const uint32_t tile_y = blockIdx.y / P.ncy, ry = blockIdx.y - tile_y * P.ncy;
+    const lattice_block blk(P);
     for (uint32_t r = threadIdx.x; r < DN_WIN * DN_WIN; r += 256) {
-        const uint32_t wy = r / DN_WIN, wx = r - wy * DN_WIN;
-        // lattice coordinates of the record; the window starts 2 before the tile
-        const int64_t lx = (int64_t)(tile_x * 16 + wx) - 2, ly = (int64_t)(tile_y * 16 + wy) - 2;
-        const int64_t qx = (int64_t)rx + lx * (int64_t)P.step, qy = (int64_t)ry + ly * (int64_t)P.step;
+        uint32_t slot;
+        size_t iq;
         float4 c = make_float4(0, 0, 0, 0), ga = c, gb = c;
-        if (lx >= 0 && ly >= 0 && qx < (int64_t)P.w && qy < (int64_t)P.h) {
-            const size_t iq = (size_t)qy * P.w + (size_t)qx;
+        if (blk.record(P, r, slot, iq)) {
             c = LoadColor<FIRST>(in, iq);
             ga = guides[2 * iq];
             gb = guides[2 * iq + 1];
         }
-        sc[wy * DN_ROW + wx] = c;      // outside the image: .w = 0, skipped like an empty pixel
-        sa[wy * DN_ROW + wx] = ga;
-        sb[wy * DN_ROW + wx] = gb;
+        sc[slot] = c;      // outside the image: .w = 0, skipped like an empty pixel
+        sa[slot] = ga;
+        sb[slot] = gb;
     }
     __syncthreads();
-    const uint32_t tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
-    const uint64_t x = (uint64_t)rx + (uint64_t)(tile_x * 16 + tx) * P.step;
-    const uint64_t y = (uint64_t)ry + (uint64_t)(tile_y * 16 + ty) * P.step;
-    if (x >= P.w || y >= P.h) return;
-    const size_t ip = (size_t)y * P.w + (size_t)x;
-    const uint32_t ic = (ty + 2) * DN_ROW + tx + 2;
+    uint32_t ic;
+    size_t ip;
+    if (!blk.pixel(P, ic, ip)) return;
     float4 cp = sc[ic];
     if (!(cp.w > 0.0f)) { out[ip] = make_float4(0, 0, 0, 0); return; }
     const pt_denoise_pixel p = MakePixel(cp, sa[ic], sb[ic]);
@@ -280,6 +319,179 @@ __global__ __launch_bounds__(256) void denoise_mean_kernel(const float4* __restr
     out[i] = LoadColor<true>(accum, i);
 }
 
+// --- the variance-guided filter over two half renders --------
+//
+// Working image between the launches: one float4 {c.xyz, v} per pixel, v the
+// variance of the pixel's luminance.  v is never negative (a square, or sums
+// of products of squares and non-negative weights, or NaN), so an empty pixel
+// is marked by .w = -1 and a pixel is filled iff !(.w < 0).  The last launch
+// writes the sample-buffer form instead: .w = 1, or 0, 0, 0, 0 where empty.
+
+PT_DEV float4 PairEmpty(bool final) { return make_float4(0, 0, 0, final ? 0.0f : -1.0f); }
+
+// The working record of pixel i before the prefilter: {c_0, raw variance}.
+PT_DEV float4 PairBegin(const float4* __restrict__ A, const float4* __restrict__ B, size_t i)
+{
+    const float4 a = A[i], b = B[i];
+    const float av[4] = {a.x, a.y, a.z, a.w}, bv[4] = {b.x, b.y, b.z, b.w};
+    const pt_denoise_pair_start s = pt_denoise_pair_begin(av, bv);
+    if (!s.filled) return PairEmpty(false);
+    return make_float4(s.c.x, s.c.y, s.c.z, s.v);
+}
+
+// Prepare: c_0 and the 3x3-prefiltered variance v_0.  The block stages the
+// 18x18 records around its 16x16 pixels in LDS, so the divisions behind a
+// pixel's c_0 and raw variance are done once (1.27 x per pixel with the halo)
+// and not once per tap (9 x), and A and B are read once; row stride as below.
+// FINAL (Iterations = 0): c_0 straight in the sample-buffer form, no prefilter.
+constexpr uint32_t PP_WIN = 18;
+constexpr uint32_t PP_ROW = 32;
+
+template <bool FINAL>
+__global__ __launch_bounds__(256) void denoise_pair_prepare_kernel(const float4* __restrict__ A,
+                                                                   const float4* __restrict__ B,
+                                                                   const float4* __restrict__ guides, uint32_t w,
+                                                                   uint32_t h, float4* __restrict__ out)
+{
+    const uint32_t tx = threadIdx.x & 15u, ty = threadIdx.x >> 4;
+    const uint32_t x = blockIdx.x * 16 + tx, y = blockIdx.y * 16 + ty;
+    if constexpr (FINAL) {
+        if (x >= w || y >= h) return;
+        const size_t ip = (size_t)y * w + x;
+        const float4 c = PairBegin(A, B, ip);
+        out[ip] = c.w < 0.0f ? PairEmpty(true) : make_float4(c.x, c.y, c.z, 1.0f);
+    } else {
+        __shared__ float4 sc[PP_WIN * PP_ROW];
+        __shared__ uint32_t ss[PP_WIN * PP_ROW];
+        for (uint32_t r = threadIdx.x; r < PP_WIN * PP_WIN; r += 256) {
+            const uint32_t wy = r / PP_WIN, wx = r - wy * PP_WIN;
+            const int64_t qx = (int64_t)(blockIdx.x * 16 + wx) - 1, qy = (int64_t)(blockIdx.y * 16 + wy) - 1;
+            float4 c = PairEmpty(false);       // outside the image: skipped like an empty pixel
+            uint32_t shape = 0;
+            if (qx >= 0 && qy >= 0 && qx < (int64_t)w && qy < (int64_t)h) {
+                const size_t iq = (size_t)qy * w + (size_t)qx;
+                c = PairBegin(A, B, iq);
+                shape = __float_as_uint(guides[2 * iq + 1].w);
+            }
+            sc[wy * PP_ROW + wx] = c;
+            ss[wy * PP_ROW + wx] = shape;
+        }
+        __syncthreads();
+        if (x >= w || y >= h) return;
+        const size_t ip = (size_t)y * w + x;
+        const uint32_t ic = (ty + 1) * PP_ROW + tx + 1;
+        const float4 cp = sc[ic];
+        if (cp.w < 0.0f) { out[ip] = PairEmpty(false); return; }
+        const uint32_t shape = ss[ic];
+        float sv = 0.0f, sk = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; dy++) {
+#pragma unroll
+            for (int dx = -1; dx <= 1; dx++) {
+                const uint32_t iq = (uint32_t)((int)ic + dy * (int)PP_ROW + dx);
+                const float v = sc[iq].w;
+                if (v < 0.0f || ss[iq] != shape) continue;
+                const float k = pt_denoise_k3(dx + 1) * pt_denoise_k3(dy + 1);
+                sv = sv + k * v;
+                sk = sk + k;
+            }
+        }
+        out[ip] = make_float4(cp.x, cp.y, cp.z, sv / sk);
+    }
+}
+
+struct pair_sums { float x, y, z, w, v; };
+
+// One tap that lies inside the image: skipped when empty or of another shape.
+PT_DEV void PairTap(pair_sums& A, const pt_denoise_pixel& p, float D, float4 c, float4 ga, float4 gb, int dx, int dy,
+                    const pt_denoise_pair_sigmas& sg)
+{
+    if (c.w < 0.0f || __float_as_uint(gb.w) != p.shape) return;
+    pt_denoise_pixel q = MakePixel(c, ga, gb);
+    float hk = pt_denoise_k(dx + 2) * pt_denoise_k(dy + 2);
+    float w = pt_denoise_pair_weight(hk, &p, &q, D, &sg);
+    A.x = A.x + w * q.c.x;
+    A.y = A.y + w * q.c.y;
+    A.z = A.z + w * q.c.z;
+    A.w = A.w + w;
+    A.v = A.v + (w * w) * c.w;
+}
+
+template <bool LAST>
+PT_DEV float4 PairResult(const pair_sums& A)
+{
+    return make_float4(A.x / A.w, A.y / A.w, A.z / A.w, LAST ? 1.0f : A.v / (A.w * A.w));
+}
+
+template <bool LAST>
+__global__ __launch_bounds__(256) void denoise_pair_gather_kernel(const float4* __restrict__ in,
+                                                                  const float4* __restrict__ guides, pair_args P,
+                                                                  float4* __restrict__ out)
+{
+    const uint32_t x = blockIdx.x * 16 + (threadIdx.x & 15u), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (x >= P.w || y >= P.h) return;
+    const size_t ip = (size_t)y * P.w + x;
+    const float4 cp = in[ip];
+    if (cp.w < 0.0f) { out[ip] = PairEmpty(LAST); return; }
+    const pt_denoise_pixel p = MakePixel(cp, guides[2 * ip], guides[2 * ip + 1]);
+    const float D = pt_denoise_pair_scale(&P.sg, cp.w);
+    pair_sums A{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    for (int dy = -2; dy <= 2; dy++) {
+        const int64_t qy = (int64_t)y + (int64_t)dy * (int64_t)P.step;
+        if (qy < 0 || qy >= (int64_t)P.h) continue;
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int64_t qx = (int64_t)x + (int64_t)dx * (int64_t)P.step;
+            if (qx < 0 || qx >= (int64_t)P.w) continue;
+            const size_t iq = (size_t)qy * P.w + (size_t)qx;
+            PairTap(A, p, D, in[iq], guides[2 * iq], guides[2 * iq + 1], dx, dy, P.sg);
+        }
+    }
+    out[ip] = PairResult<LAST>(A);
+}
+
+// The lattice kernel's window and arrays; the variance rides in the colour
+// record's .w, so the LDS footprint is the single-buffer kernel's.
+template <bool LAST>
+__global__ __launch_bounds__(256) void denoise_pair_lattice_kernel(const float4* __restrict__ in,
+                                                                   const float4* __restrict__ guides, pair_args P,
+                                                                   float4* __restrict__ out)
+{
+    __shared__ float4 sc[DN_WIN * DN_ROW], sa[DN_WIN * DN_ROW], sb[DN_WIN * DN_ROW];
+    const lattice_block blk(P);
+    for (uint32_t r = threadIdx.x; r < DN_WIN * DN_WIN; r += 256) {
+        uint32_t slot;
+        size_t iq;
+        float4 c = PairEmpty(false), ga = make_float4(0, 0, 0, 0), gb = ga;
+        if (blk.record(P, r, slot, iq)) {
+            c = in[iq];
+            ga = guides[2 * iq];
+            gb = guides[2 * iq + 1];
+        }
+        sc[slot] = c;      // outside the image: .w = -1, skipped like an empty pixel
+        sa[slot] = ga;
+        sb[slot] = gb;
+    }
+    __syncthreads();
+    uint32_t ic;
+    size_t ip;
+    if (!blk.pixel(P, ic, ip)) return;
+    const float4 cp = sc[ic];
+    if (cp.w < 0.0f) { out[ip] = PairEmpty(LAST); return; }
+    const pt_denoise_pixel p = MakePixel(cp, sa[ic], sb[ic]);
+    const float D = pt_denoise_pair_scale(&P.sg, cp.w);
+    pair_sums A{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const uint32_t iq = (uint32_t)((int)ic + dy * (int)DN_ROW + dx);
+            PairTap(A, p, D, sc[iq], sa[iq], sb[iq], dx, dy, P.sg);
+        }
+    }
+    out[ip] = PairResult<LAST>(A);
+}
+
 }  // namespace ptd
 
 uint32_t pt_guides_stack_cap() { return 20; }
@@ -299,27 +511,33 @@ hipError_t pt_launch_denoise_guides(const ptd::dscene& S, uint32_t camera_index,
     return hipGetLastError();
 }
 
+// Iteration `iteration`'s geometry and the launch grid of its kernel variant.
+static dim3 FilterGrid(ptd::filter_grid& P, uint32_t w, uint32_t h, uint32_t iteration, bool lattice)
+{
+    P.w = w;
+    P.h = h;
+    P.step = 1u << iteration;
+    P.ncx = P.step < w ? P.step : w;
+    P.ncy = P.step < h ? P.step : h;
+    if (!lattice) return dim3((w + 15) / 16, (h + 15) / 16);
+    // 16x16 lattice tiles of the largest residue class (rx = ry = 0); the
+    // smaller classes leave their last tiles partly or wholly idle.
+    uint32_t lw = (w + P.step - 1) / P.step, lh = (h + P.step - 1) / P.step;
+    return dim3(P.ncx * ((lw + 15) / 16), P.ncy * ((lh + 15) / 16));
+}
+
 hipError_t pt_launch_denoise(const float4* in, bool accumulator, const float4* guides, uint32_t w, uint32_t h,
                              const pt_denoise_parameters* p, uint32_t iteration, bool lattice, float4* out,
                              hipStream_t st)
 {
     if (w == 0 || h == 0) return hipSuccess;
     ptd::denoise_args P;
-    P.w = w;
-    P.h = h;
-    P.step = 1u << iteration;
+    const dim3 grid = FilterGrid(P, w, h, iteration, lattice);
     P.sg = pt_denoise_iteration_sigmas(p, iteration);
-    P.ncx = P.step < w ? P.step : w;
-    P.ncy = P.step < h ? P.step : h;
     if (lattice) {
-        // 16x16 lattice tiles of the largest residue class (rx = ry = 0); the
-        // smaller classes leave their last tiles partly or wholly idle.
-        uint32_t lw = (w + P.step - 1) / P.step, lh = (h + P.step - 1) / P.step;
-        dim3 grid(P.ncx * ((lw + 15) / 16), P.ncy * ((lh + 15) / 16));
         if (accumulator) hipLaunchKernelGGL(ptd::denoise_lattice_kernel<true>, grid, dim3(256), 0, st, in, guides, P, out);
         else hipLaunchKernelGGL(ptd::denoise_lattice_kernel<false>, grid, dim3(256), 0, st, in, guides, P, out);
     } else {
-        dim3 grid((w + 15) / 16, (h + 15) / 16);
         if (accumulator) hipLaunchKernelGGL(ptd::denoise_gather_kernel<true>, grid, dim3(256), 0, st, in, guides, P, out);
         else hipLaunchKernelGGL(ptd::denoise_gather_kernel<false>, grid, dim3(256), 0, st, in, guides, P, out);
     }
@@ -330,5 +548,33 @@ hipError_t pt_launch_denoise_mean(const float4* accum, uint32_t n, float4* out, 
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(ptd::denoise_mean_kernel, dim3((n + 255) / 256), dim3(256), 0, st, accum, n, out);
+    return hipGetLastError();
+}
+
+hipError_t pt_launch_denoise_pair_prepare(const float4* a, const float4* b, const float4* guides, uint32_t w,
+                                          uint32_t h, bool final, float4* out, hipStream_t st)
+{
+    if (w == 0 || h == 0) return hipSuccess;
+    dim3 grid((w + 15) / 16, (h + 15) / 16);
+    if (final) hipLaunchKernelGGL(ptd::denoise_pair_prepare_kernel<true>, grid, dim3(256), 0, st, a, b, guides, w, h, out);
+    else hipLaunchKernelGGL(ptd::denoise_pair_prepare_kernel<false>, grid, dim3(256), 0, st, a, b, guides, w, h, out);
+    return hipGetLastError();
+}
+
+hipError_t pt_launch_denoise_pair(const float4* in, const float4* guides, uint32_t w, uint32_t h,
+                                  const pt_denoise_pair_parameters* p, uint32_t iteration, bool last, bool lattice,
+                                  float4* out, hipStream_t st)
+{
+    if (w == 0 || h == 0) return hipSuccess;
+    ptd::pair_args P;
+    const dim3 grid = FilterGrid(P, w, h, iteration, lattice);
+    P.sg = pt_denoise_pair_make_sigmas(p);
+    if (lattice) {
+        if (last) hipLaunchKernelGGL(ptd::denoise_pair_lattice_kernel<true>, grid, dim3(256), 0, st, in, guides, P, out);
+        else hipLaunchKernelGGL(ptd::denoise_pair_lattice_kernel<false>, grid, dim3(256), 0, st, in, guides, P, out);
+    } else {
+        if (last) hipLaunchKernelGGL(ptd::denoise_pair_gather_kernel<true>, grid, dim3(256), 0, st, in, guides, P, out);
+        else hipLaunchKernelGGL(ptd::denoise_pair_gather_kernel<false>, grid, dim3(256), 0, st, in, guides, P, out);
+    }
     return hipGetLastError();
 }

@@ -125,6 +125,16 @@ hipError_t pt_launch_denoise(const float4* in, bool accumulator, const float4* g
                              hipStream_t st);
 // Iterations = 0: out = the accumulator's mean, .w = 1 (zeros where empty).
 hipError_t pt_launch_denoise_mean(const float4* accum, uint32_t n, float4* out, hipStream_t st);
+// The pair filter.  Prepare: accumulators a, b -> the
+// working image {c_0, prefiltered variance} (.w = -1 where a + b is empty);
+// final (Iterations = 0): c_0 in the sample-buffer form instead.  Then one
+// iteration (step 2^iteration) in -> out between working images; last: out
+// in the sample-buffer form (.w = 1, zeros where empty).
+hipError_t pt_launch_denoise_pair_prepare(const float4* a, const float4* b, const float4* guides, uint32_t w,
+                                          uint32_t h, bool final, float4* out, hipStream_t st);
+hipError_t pt_launch_denoise_pair(const float4* in, const float4* guides, uint32_t w, uint32_t h,
+                                  const pt_denoise_pair_parameters* p, uint32_t iteration, bool last, bool lattice,
+                                  float4* out, hipStream_t st);
 // Frame statistics (stats.hip) of accumulator a, or of
 // a + b with the noise fields from the pair (b != nullptr), added into *out,
 // which the caller has cleared: counts as they are, the two minima as the

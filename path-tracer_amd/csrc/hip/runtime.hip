@@ -163,7 +163,7 @@ struct pt_denoise_guides {
     pt_device* dev = nullptr;
     uint32_t width = 0, height = 0;
     dbuf<float4> records;                // 2 float4 per pixel: a pt_denoise_guide
-    dbuf<float4> scratch;                // the filter's second image (Iterations >= 2)
+    dbuf<float4> scratch;                // the filter's second image (Iterations >= 2; the pair filter: >= 1)
     dbuf<uint32_t> spill;
     dbuf<float> observe;                 // ObserveUnderD65's per-sample constants (base_color.hpp)
     uint32_t variant = PT_DENOISE_VARIANT_AUTO;
@@ -2198,6 +2198,60 @@ int ptDenoiseSampleBuffer(pt_device* d, pt_sample_buffer* src, pt_denoise_guides
                                  out, d->stream));
         if (int e = EndTimed(d, ep)) return e;
         in = out;
+    }
+    return 0;
+}
+
+// The pair filter's kernel of iteration i.  Automatic mode takes the lattice
+// kernel at every step: started as the single-buffer filter's choice carried
+// over, then measured on the pair kernels themselves, where the lattice is
+// again 1.2 - 2 x faster at each of the steps 1 .. 32.
+static bool DenoisePairLattice(uint32_t variant, uint32_t /*iteration*/)
+{
+    return variant != PT_DENOISE_VARIANT_GATHER;
+}
+
+int ptDenoiseSampleBufferPair(pt_device* d, pt_sample_buffer* a, pt_sample_buffer* b, pt_denoise_guides* g,
+                              const pt_denoise_pair_parameters* p, pt_sample_buffer* dst)
+{
+    if (!d || !a || !b || !g || !p || !dst) { SetError("null argument"); return -1; }
+    if (a == b || a == dst || b == dst) { SetError("denoise pair: a, b and dst must be three sample buffers"); return -1; }
+    if (a->dev != d || b->dev != d || dst->dev != d || g->dev != d) {
+        SetError("denoise pair: objects of another device");
+        return -1;
+    }
+    for (const pt_sample_buffer* s : {a, b, dst}) {
+        if (s->width != g->width || s->height != g->height) {
+            SetError("denoise pair: size mismatch (a %ux%u, b %ux%u, guides %ux%u, dst %ux%u)", a->width, a->height,
+                     b->width, b->height, g->width, g->height, dst->width, dst->height);
+            return -1;
+        }
+    }
+    if (!pt_denoise_pair_parameters_ok(p)) {
+        SetError("denoise pair: bad parameters (Iterations %u > %u or a sigma not > 0)", p->Iterations,
+                 (uint32_t)PT_DENOISE_MAX_ITERATIONS);
+        return -1;
+    }
+    PT_HIP(hipSetDevice(d->id));
+    const size_t n = (size_t)g->width * g->height;
+    const uint32_t N = p->Iterations;
+    if (N >= 1) PT_HIP(g->scratch.alloc(n));
+    // Image k (0: the prepare launch's, k: iteration k - 1's) is dst when an
+    // even number of launches follow it, so the last one lands in dst.
+    auto image = [&](uint32_t k) { return ((N - k) & 1u) ? g->scratch.ptr : dst->accum; };
+    {
+        event_pair ep{};
+        if (int e = BeginTimed(d, PT_KERNEL_DENOISE, ep)) return e;
+        PT_HIP(pt_launch_denoise_pair_prepare(a->accum, b->accum, g->records.ptr, g->width, g->height, N == 0,
+                                              image(0), d->stream));
+        if (int e = EndTimed(d, ep)) return e;
+    }
+    for (uint32_t i = 0; i < N; i++) {
+        event_pair ep{};
+        if (int e = BeginTimed(d, PT_KERNEL_DENOISE, ep)) return e;
+        PT_HIP(pt_launch_denoise_pair(image(i), g->records.ptr, g->width, g->height, p, i, i + 1 == N,
+                                      DenoisePairLattice(g->variant, i), image(i + 1), d->stream));
+        if (int e = EndTimed(d, ep)) return e;
     }
     return 0;
 }

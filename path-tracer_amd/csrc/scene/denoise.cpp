@@ -3,6 +3,8 @@
 // and the second implementation the device kernels (csrc/hip/denoise.hip) are
 // compared with: the same definition, the same per-tap arithmetic
 // (include/pt_denoise.h), the same tap order.  Single-threaded.
+// ptsDenoisePair is the same for the variance-guided filter over two half
+// renders and ptDenoiseSampleBufferPair.
 #include "../../../include/pt_scene.h"
 #include "../../../include/pt_denoise.h"
 
@@ -56,7 +58,104 @@ void Iterate(uint32_t W, uint32_t H, const px4* in, const pt_denoise_guide* guid
     }
 }
 
+// --- the variance-guided filter over two half renders ---
+
+struct pair_px { float x, y, z, v; bool filled; };   // colour, variance of its luminance
+
+// c_0 and the prefiltered variance v_0 of S = A + B.
+void PairPrepare(uint32_t W, uint32_t H, const float* A, const float* B, const pt_denoise_guide* guides, pair_px* out)
+{
+    const size_t n = (size_t)W * H;
+    std::vector<float> raw(n);
+    for (size_t i = 0; i < n; i++) {
+        const pt_denoise_pair_start s = pt_denoise_pair_begin(A + 4 * i, B + 4 * i);
+        out[i] = {s.c.x, s.c.y, s.c.z, 0.0f, s.filled != 0};
+        raw[i] = s.v;
+    }
+    for (uint32_t y = 0; y < H; y++) {
+        for (uint32_t x = 0; x < W; x++) {
+            const size_t ip = (size_t)y * W + x;
+            if (!out[ip].filled) continue;
+            float sv = 0.0f, sk = 0.0f;
+            for (int dy = -1; dy <= 1; dy++) {
+                const int64_t qy = (int64_t)y + dy;
+                if (qy < 0 || qy >= (int64_t)H) continue;
+                for (int dx = -1; dx <= 1; dx++) {
+                    const int64_t qx = (int64_t)x + dx;
+                    if (qx < 0 || qx >= (int64_t)W) continue;
+                    const size_t iq = (size_t)qy * W + (size_t)qx;
+                    if (!out[iq].filled || guides[iq].shape != guides[ip].shape) continue;
+                    const float k = pt_denoise_k3(dx + 1) * pt_denoise_k3(dy + 1);
+                    sv = sv + k * raw[iq];
+                    sk = sk + k;
+                }
+            }
+            out[ip].v = sv / sk;
+        }
+    }
+}
+
+void PairIterate(uint32_t W, uint32_t H, const pair_px* in, const pt_denoise_guide* guides,
+                 const pt_denoise_pair_sigmas& sg, uint32_t step, pair_px* out)
+{
+    for (uint32_t y = 0; y < H; y++) {
+        for (uint32_t x = 0; x < W; x++) {
+            const size_t ip = (size_t)y * W + x;
+            if (!in[ip].filled) { out[ip] = {0, 0, 0, 0, false}; continue; }
+            const pt_denoise_pixel p = Pixel({in[ip].x, in[ip].y, in[ip].z, 1.0f}, guides[ip]);
+            const float D = pt_denoise_pair_scale(&sg, in[ip].v);
+            float sx = 0.0f, sy = 0.0f, sz = 0.0f, sw = 0.0f, sv = 0.0f;
+            for (int dy = -2; dy <= 2; dy++) {
+                const int64_t qy = (int64_t)y + (int64_t)dy * step;
+                if (qy < 0 || qy >= (int64_t)H) continue;
+                for (int dx = -2; dx <= 2; dx++) {
+                    const int64_t qx = (int64_t)x + (int64_t)dx * step;
+                    if (qx < 0 || qx >= (int64_t)W) continue;
+                    const size_t iq = (size_t)qy * W + (size_t)qx;
+                    if (!in[iq].filled || guides[iq].shape != p.shape) continue;
+                    const pt_denoise_pixel q = Pixel({in[iq].x, in[iq].y, in[iq].z, 1.0f}, guides[iq]);
+                    const float h = pt_denoise_k(dx + 2) * pt_denoise_k(dy + 2);
+                    const float w = pt_denoise_pair_weight(h, &p, &q, D, &sg);
+                    sx = sx + w * q.c.x;
+                    sy = sy + w * q.c.y;
+                    sz = sz + w * q.c.z;
+                    sw = sw + w;
+                    sv = sv + (w * w) * in[iq].v;
+                }
+            }
+            out[ip] = {sx / sw, sy / sw, sz / sw, sv / (sw * sw), true};
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int ptsDenoisePair(uint32_t width, uint32_t height, const float* accum_a, const float* accum_b,
+                              const pt_denoise_guide* guides, const pt_denoise_pair_parameters* params,
+                              float* out_rgba)
+{
+    if (!accum_a || !accum_b || !guides || !params || !out_rgba || width == 0 || height == 0) return -1;
+    if (accum_a == accum_b) return -1;
+    if (!pt_denoise_pair_parameters_ok(params)) return -1;
+    const size_t n = (size_t)width * height;
+    try {
+        std::vector<pair_px> a(n), b(params->Iterations ? n : 0);
+        PairPrepare(width, height, accum_a, accum_b, guides, a.data());
+        const pt_denoise_pair_sigmas sg = pt_denoise_pair_make_sigmas(params);
+        for (uint32_t i = 0; i < params->Iterations; i++) {
+            PairIterate(width, height, a.data(), guides, sg, 1u << i, b.data());
+            a.swap(b);
+        }
+        for (size_t i = 0; i < n; i++) {
+            float* o = out_rgba + 4 * i;
+            if (a[i].filled) { o[0] = a[i].x; o[1] = a[i].y; o[2] = a[i].z; o[3] = 1.0f; }
+            else { o[0] = o[1] = o[2] = o[3] = 0.0f; }
+        }
+    } catch (const std::bad_alloc&) {
+        return -2;
+    }
+    return 0;
+}
 
 extern "C" int ptsDenoise(uint32_t width, uint32_t height, const float* accum_rgba, const pt_denoise_guide* guides,
                           const pt_denoise_parameters* params, float* out_rgba)

@@ -351,6 +351,50 @@ def denoise_host(accum: np.ndarray, guides: np.ndarray, params: "DenoiseParamete
     return out
 
 
+class DenoisePairParameters:
+    """pt_denoise_pair_parameters (pt_packed.h): the variance-guided filter
+    over two half renders.  SigmaLuminance is in standard deviations of the
+    pixel's luminance, estimated from the two halves; the other sigmas are
+    DenoiseParameters'.  The defaults are the ones chosen on configs 1, 2, 3
+    and 5 at 2x4, 2x32 and 2x128 rounds against 2048."""
+
+    def __init__(self, Iterations: int = 5, SigmaLuminance: float = 4.0, SigmaNormal: float = 0.25,
+                 SigmaDepth: float = 0.3, SigmaAlbedo: float = 0.1):
+        self.Iterations = int(Iterations)
+        self.SigmaLuminance, self.SigmaNormal = float(SigmaLuminance), float(SigmaNormal)
+        self.SigmaDepth, self.SigmaAlbedo = float(SigmaDepth), float(SigmaAlbedo)
+
+    def as_struct(self) -> N.pt_denoise_pair_parameters:
+        return N.pt_denoise_pair_parameters(self.Iterations, self.SigmaLuminance, self.SigmaNormal, self.SigmaDepth,
+                                            self.SigmaAlbedo)
+
+
+def denoise_pair_host(accum_a: np.ndarray, accum_b: np.ndarray, guides: np.ndarray,
+                      params: "DenoisePairParameters | None" = None) -> np.ndarray:
+    """The variance-guided denoiser on the CPU (ptsDenoisePair,
+    libptscene.so), which the device filter equals bit for bit.  accum_a,
+    accum_b: (H, W, 4) accumulators of two independent renders of one frame
+    (FrameIndex apart by 1 << 24); guides: (H, W) DENOISE_GUIDE_DTYPE records.
+    Returns (H, W, 4): the denoised mean XYZ of a + b and 1 (zeros where the
+    combined count is not positive)."""
+    a = np.ascontiguousarray(accum_a, dtype=np.float32)
+    b = np.ascontiguousarray(accum_b, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"accumulator of shape {a.shape}, expected (H, W, 4)")
+    if b.shape != a.shape:
+        raise ValueError(f"second accumulator of shape {b.shape}, first {a.shape}")
+    g = np.ascontiguousarray(guides, dtype=N.DENOISE_GUIDE_DTYPE)
+    if g.shape != a.shape[:2]:
+        raise ValueError(f"guides of shape {g.shape}, accumulator {a.shape[:2]}")
+    out = np.zeros_like(a)
+    p = (params or DenoisePairParameters()).as_struct()
+    rc = N.scene_lib().ptsDenoisePair(a.shape[1], a.shape[0], N.fptr(a), N.fptr(b), g.ctypes.data, C.byref(p),
+                                      N.fptr(out))
+    if rc != 0:
+        raise PathTracerError(f"ptsDenoisePair: bad arguments (status {rc})")
+    return out
+
+
 class DenoiseGuides:
     """Per-pixel primary-hit records of the scene camera's central rays
     (normal, hit time, base colour, shape) that steer the denoiser, plus the
@@ -436,6 +480,26 @@ class SampleBuffer:
         try:
             _check(N.hip_lib().ptDenoiseSampleBuffer(self.device.handle, self._h, guides.handle, C.byref(p),
                                                      dst.handle), "ptDenoiseSampleBuffer")
+        except PathTracerError:
+            if out is None:
+                dst.close()
+            raise
+        return dst
+
+    def denoise_pair(self, other: "SampleBuffer", guides: "DenoiseGuides",
+                     params: "DenoisePairParameters | None" = None,
+                     out: "SampleBuffer | None" = None) -> "SampleBuffer":
+        """The variance-guided filter on the device (ptDenoiseSampleBufferPair;
+        enqueues) over this buffer and `other`, two independent renders of one
+        frame (e.g. render_until_noise's halves): `out` (a new sample buffer
+        of this size when None) receives the denoised mean XYZ of this + other
+        and a sample count of 1, as denoise() leaves it.  Neither input is
+        written."""
+        dst = out if out is not None else SampleBuffer(self.device, self.width, self.height)
+        p = (params or DenoisePairParameters()).as_struct()
+        try:
+            _check(N.hip_lib().ptDenoiseSampleBufferPair(self.device.handle, self._h, other.handle, guides.handle,
+                                                         C.byref(p), dst.handle), "ptDenoiseSampleBufferPair")
         except PathTracerError:
             if out is None:
                 dst.close()

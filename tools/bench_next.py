@@ -13,7 +13,9 @@
 * denoise (ptDenoiseSampleBuffer, denoise.hip): ms per a-trous
   iteration (step 1 .. 32) of the gather and the lattice kernel and of the
   automatic choice, ms per 5-iteration call, and the guide kernel, on C3 at
-  1920x1080 and 3840x2160.
+  1920x1080 and 3840x2160; in the same run the pair filter
+  (ptDenoiseSampleBufferPair, §6 row 7) on two 8-round halves: ms per step
+  and variant, per 5-iteration call, and its prepare launch.
 * stats (ptComputeFrameStatistics, stats.hip): kernel ms
   of the statistics pass, single and pair, with and without the wave-uniform
   shortcut, on C3's accumulator after 8 rounds and on a constant image, with
@@ -86,7 +88,8 @@ def denoise(pt, dev):
     """Per size: guides_ms; per variant the kernel time of each step (the
     difference between the summed launches of k and of k - 1 iterations: an
     iteration's step and constants depend on its index only) and of a
-    5-iteration call, with its wall time."""
+    5-iteration call, with its wall time; then the same for the pair filter
+    (pair_* keys)."""
     out = {}
     scene = pt.Scene.config(3)
     ds = pt.DeviceScene(dev)
@@ -115,8 +118,34 @@ def denoise(pt, dev):
                     res[f"{name}_call5_ms"] = round(ms * k, 4)
                     res[f"{name}_call5_wall_ms"] = round(wall, 4)
             res[f"{name}_step_ms"] = {str(1 << (k - 1)): round(total[k] - total[k - 1], 4) for k in range(1, 7)}
+        # The pair filter on two halves (FrameIndex 0 and 1 << 24, 8 rounds
+        # each) in the same run.  All its launches count under one kernel id,
+        # so the summed time of k iterations holds the prepare launch: steps
+        # >= 2 are differences as above; pair_*_prepare_plus_step1_ms is the
+        # Iterations = 1 call (prepare with the prefilter + step 1) and
+        # pair_*_mean_ms the Iterations = 0 call (prepare without prefilter).
+        sb2 = pt.SampleBuffer(dev, W, H)
+        r2 = pt.BasicRenderer(dev, ds, sb2)
+        r2.RenderFlags = 3
+        r2.FrameIndex = 1 << 24
+        r2.reset()
+        r2.run(8)
+        for name, variant in variants.items():
+            guides.set_variant(variant)
+            total = []
+            for k in range(0, 7):
+                p = pt.DenoisePairParameters(Iterations=k)
+                sb.denoise_pair(sb2, guides, p, out=dst)   # warm
+                ms, wall = timed(dev, K_DENOISE, lambda: sb.denoise_pair(sb2, guides, p, out=dst), 10)
+                total.append(ms * (k + 1))                 # k iterations + the prepare launch
+                if k == 5:
+                    res[f"pair_{name}_call5_ms"] = round(ms * (k + 1), 4)
+                    res[f"pair_{name}_call5_wall_ms"] = round(wall, 4)
+            res[f"pair_{name}_mean_ms"] = round(total[0], 4)          # Iterations = 0: c_0 only
+            res[f"pair_{name}_prepare_plus_step1_ms"] = round(total[1], 4)
+            res[f"pair_{name}_step_ms"] = {str(1 << (k - 1)): round(total[k] - total[k - 1], 4) for k in range(2, 7)}
         out[f"{W}x{H}"] = res
-        for x in (guides, r, dst, sb):
+        for x in (guides, r2, sb2, r, dst, sb):
             x.close()
     ds.close()
     return out
