@@ -30,8 +30,10 @@
  * one-process-per-GPU rendering, a denoiser (guide images + an
  * edge-avoiding a-trous filter) in front of ptRenderSampleBuffer, frame
  * statistics (luminance histogram, automatic exposure, a noise estimate from
- * two half renders), and a variance-guided form of the denoiser that takes
- * those two half renders (ptDenoiseSampleBufferPair).
+ * two half renders), a variance-guided form of the denoiser that takes
+ * those two half renders (ptDenoiseSampleBufferPair), and temporal
+ * reprojection of an accumulator into a new view (ptReprojectSampleBuffer),
+ * which keeps a frame's history across a camera move.
  *
  * Conventions: creators return NULL on failure and set ptGetLastError();
  * other calls return 0 on success or a non-zero status (HIP / RCCL error
@@ -106,7 +108,8 @@ enum {
     PT_KERNEL_DENOISE = 7,   /* one a-trous iteration of ptDenoiseSampleBuffer */
     PT_KERNEL_GUIDES  = 8,   /* ptRenderDenoiseGuides */
     PT_KERNEL_STATS   = 9,   /* ptComputeFrameStatistics' pass and ptAccumulateSampleBuffer's add */
-    PT_KERNEL_COUNT   = 10,
+    PT_KERNEL_REPROJECT = 10, /* ptReprojectSampleBuffer */
+    PT_KERNEL_COUNT   = 11,
 };
 
 /* resolve_parameters (src/integrator/integrator.hpp:12-48). */
@@ -432,6 +435,32 @@ int  ptSetDenoiseVariant(pt_denoise_guides* guides, uint32_t variant);
  * device, when Iterations > 8 or when a sigma is not > 0. */
 int  ptDenoiseSampleBufferPair(pt_device* device, pt_sample_buffer* a, pt_sample_buffer* b, pt_denoise_guides* guides,
                                const pt_denoise_pair_parameters* params, pt_sample_buffer* dst);
+
+/* Temporal reprojection (no reference counterpart; definition, kernel design
+ * and measured times in DESIGN.md §6 row 8; arithmetic in pt_reproject.h):
+ * carries a frame's history across a camera move or a resize.  prev is the
+ * accumulator of the previous view, prev_guides its guide records and
+ * *prev_camera the packed camera record they were rendered with (the caller
+ * keeps it: the scene has been updated since); guides and *camera are the
+ * current view's.  Every pixel of dst receives the bilinear blend of the
+ * previous accumulator's taps that still show its surface (same shape, normal
+ * and distance within the parameters' bounds), as (mean XYZ * n, n) with n
+ * the carried sample count capped at MaxHistory, or 0, 0, 0, 0 where the
+ * pixel is disoccluded.  dst is an accumulator: a renderer with
+ * PT_RENDER_FLAG_ACCUMULATE adds new samples on top of it.  Call it after the
+ * frame's ptResetBasicRenderer, whose raygen clears dst, and before its
+ * ptRunBasicRenderer.  Enqueues one launch (PT_KERNEL_REPROJECT) and returns,
+ * like ptDenoiseSampleBuffer; both cameras are read during the call.  prev
+ * and both guides objects are not
+ * written; two calls on the same inputs give the same bits, and the result
+ * equals ptsReproject's (pt_scene.h) bit for bit.  Fails, launching and
+ * writing nothing, on a NULL argument, prev == dst, prev_guides == guides,
+ * an object of another device, prev and prev_guides (or dst and guides) of
+ * different sizes, or a parameter outside its range (pt_packed.h). */
+int  ptReprojectSampleBuffer(pt_device* device, pt_sample_buffer* prev, pt_denoise_guides* prev_guides,
+                             const pt_packed_camera* prev_camera, pt_denoise_guides* guides,
+                             const pt_packed_camera* camera, const pt_reproject_parameters* params,
+                             pt_sample_buffer* dst);
 
 /* Frame statistics (no reference counterpart; definition, kernel design and
  * measured times in DESIGN.md §6 row 6; helpers that read the result in

@@ -222,6 +222,16 @@ typedef struct pt_denoise_pair_parameters {
     float    SigmaAlbedo;              /* > 0 */
 } pt_denoise_pair_parameters;
 
+/* Temporal reprojection (arithmetic in pt_reproject.h):
+ * which taps of the previous frame still show the current pixel's surface,
+ * and how much history a pixel may carry. */
+typedef struct pt_reproject_parameters {
+    float    NormalCosine;             /* in (-1, 1], default 0.9: smallest dot product of the two normals */
+    float    DepthTolerance;           /* > 0, default 0.05: largest relative mismatch of the distance */
+    float    MinWeight;                /* in (0, 1], default 0.25: smallest sum of valid bilinear weights */
+    float    MaxHistory;               /* > 0, default 64 (+inf: none): cap on the carried sample count */
+} pt_reproject_parameters;
+
 /* Frame statistics (no reference counterpart; definition in DESIGN.md §6 row
  * 6, arithmetic in pt_stats.h): integer counts and float min/max of one
  * accumulator, or of the sum A + B of two with the noise fields taken from
@@ -250,6 +260,7 @@ static_assert(sizeof(pt_frame_statistics) == 2120, "frame_statistics");
 static_assert(sizeof(pt_denoise_guide) == 32, "denoise_guide");
 static_assert(sizeof(pt_denoise_parameters) == 20, "denoise_parameters");
 static_assert(sizeof(pt_denoise_pair_parameters) == 20, "denoise_pair_parameters");
+static_assert(sizeof(pt_reproject_parameters) == 16, "reproject_parameters");
 static_assert(sizeof(pt_packed_transform) == 128, "packed_transform");
 static_assert(sizeof(pt_packed_texture) == 32, "packed_texture");
 static_assert(sizeof(pt_packed_shape) == 144, "packed_shape");

@@ -188,6 +188,27 @@ int  ptsDenoise(uint32_t width, uint32_t height, const float* accum_rgba, const 
 int  ptsDenoisePair(uint32_t width, uint32_t height, const float* accum_a, const float* accum_b,
                     const pt_denoise_guide* guides, const pt_denoise_pair_parameters* params, float* out_rgba);
 
+/* Temporal reprojection on the host (no reference counterpart; definition in
+ * DESIGN.md §6 row 8, arithmetic in pt_reproject.h): the CPU path and the
+ * implementation ptReprojectSampleBuffer (pt_api.h) is compared with, bit for
+ * bit.  prev_accum, prev_guides, prev_camera: the previous view's accumulator
+ * (prev_width x prev_height), guide records and packed camera; guides,
+ * camera: the current view's (width x height).  out_rgba receives
+ * (mean XYZ * n, n) per current pixel, 0, 0, 0, 0 without a history.  Returns
+ * non-zero, leaving out_rgba untouched, on a NULL argument, an empty image,
+ * prev_accum == out_rgba, prev_guides == guides or a parameter outside its
+ * range (pt_packed.h).  Single-threaded. */
+int  ptsReproject(uint32_t prev_width, uint32_t prev_height, const float* prev_accum,
+                  const pt_denoise_guide* prev_guides, const pt_packed_camera* prev_camera, uint32_t width,
+                  uint32_t height, const pt_denoise_guide* guides, const pt_packed_camera* camera,
+                  const pt_reproject_parameters* params, float* out_rgba);
+/* pt_reproject.h's central camera ray of pixel (x, y) of a width x height
+ * frame (the guide kernel's ray: pixel centre, lens centre, the velocity
+ * after its packed round trip).  Non-zero on a NULL argument, an empty frame
+ * or an unknown camera model. */
+int  ptsCentralCameraRay(const pt_packed_camera* camera, uint32_t x, uint32_t y, uint32_t width, uint32_t height,
+                         float origin[3], float velocity[3]);
+
 /* Frame statistics on the host (no reference counterpart; definition in
  * DESIGN.md §6 row 6, arithmetic in pt_stats.h): the CPU path for saved
  * accumulators and the implementation ptComputeFrameStatistics (pt_api.h) is

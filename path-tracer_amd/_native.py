@@ -99,6 +99,16 @@ class pt_denoise_pair_parameters(C.Structure):
     ]
 
 
+class pt_reproject_parameters(C.Structure):
+    """pt_reproject_parameters (include/pt_packed.h)."""
+    _fields_ = [
+        ("NormalCosine", C.c_float),
+        ("DepthTolerance", C.c_float),
+        ("MinWeight", C.c_float),
+        ("MaxHistory", C.c_float),
+    ]
+
+
 STATS_BINS = 256
 
 
@@ -123,6 +133,19 @@ class pt_frame_statistics(C.Structure):
 
 class pt_packed_transform(C.Structure):
     _fields_ = [("To", C.c_float * 16), ("From", C.c_float * 16)]
+
+
+class pt_packed_camera(C.Structure):
+    """pt_packed_camera (include/pt_packed.h); CAMERA_DTYPE is the same record in numpy."""
+    _fields_ = [
+        ("Model", C.c_uint32),
+        ("FocalLength", C.c_float),
+        ("ApertureRadius", C.c_float),
+        ("SensorDistance", C.c_float),
+        ("SensorSize", C.c_float * 2),
+        ("Pad0", C.c_uint32 * 2),
+        ("Transform", pt_packed_transform),
+    ]
 
 
 class pt_preview_parameters(C.Structure):
@@ -210,6 +233,7 @@ DENOISE_MAX_ITERATIONS = 8
 DENOISE_VARIANT_AUTO, DENOISE_VARIANT_GATHER, DENOISE_VARIANT_LATTICE = 0, 1, 2
 KERNEL_STATS = 9     # the frame statistics pass and the sample-buffer add (PT_KERNEL_STATS)
 STATS_VARIANT_AUTO, STATS_VARIANT_PLAIN, STATS_VARIANT_UNIFORM = 0, 1, 2
+KERNEL_REPROJECT = 10   # ptReprojectSampleBuffer (PT_KERNEL_REPROJECT)
 
 _vp = C.c_void_p
 _u32 = C.c_uint32
@@ -275,6 +299,9 @@ SCENE_API = {
     "ptsSetSpectrumTablePath": (None, [C.c_char_p]),
     "ptsDenoise": (_i32, [_u32, _u32, _fptr, _vp, C.POINTER(pt_denoise_parameters), _fptr]),
     "ptsDenoisePair": (_i32, [_u32, _u32, _fptr, _fptr, _vp, C.POINTER(pt_denoise_pair_parameters), _fptr]),
+    "ptsReproject": (_i32, [_u32, _u32, _fptr, _vp, C.POINTER(pt_packed_camera), _u32, _u32, _vp,
+                            C.POINTER(pt_packed_camera), C.POINTER(pt_reproject_parameters), _fptr]),
+    "ptsCentralCameraRay": (_i32, [C.POINTER(pt_packed_camera), _u32, _u32, _u32, _u32, _fptr, _fptr]),
     "ptsFrameStatistics": (_i32, [_u32, _u32, _fptr, _fptr, C.POINTER(pt_frame_statistics)]),
     "ptsStatsBin": (_i32, [C.c_float]),
     "ptsStatsBinEdge": (C.c_double, [_i32]),
@@ -345,6 +372,8 @@ HIP_API = {
     "ptDenoiseSampleBuffer": (_i32, [_vp, _vp, _vp, C.POINTER(pt_denoise_parameters), _vp]),
     "ptSetDenoiseVariant": (_i32, [_vp, _u32]),
     "ptDenoiseSampleBufferPair": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(pt_denoise_pair_parameters), _vp]),
+    "ptReprojectSampleBuffer": (_i32, [_vp, _vp, _vp, C.POINTER(pt_packed_camera), _vp, C.POINTER(pt_packed_camera),
+                                       C.POINTER(pt_reproject_parameters), _vp]),
     "ptComputeFrameStatistics": (_i32, [_vp, _vp, _vp, C.POINTER(pt_frame_statistics)]),
     "ptAccumulateSampleBuffer": (_i32, [_vp, _vp, _vp]),
     "ptSetFrameStatisticsVariant": (_i32, [_vp, _u32]),

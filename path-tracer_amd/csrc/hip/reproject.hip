@@ -1,0 +1,102 @@
+// reproject.hip — temporal reprojection of an accumulator into a new view (no
+// reference counterpart).  One thread per pixel of the
+// current frame: its central camera ray, the world point its guide record
+// saw, that point's position in the previous frame, and the bilinear blend of
+// the previous accumulator's four taps that still show the same surface.  The
+// per-pixel and per-tap arithmetic is include/pt_reproject.h's, shared with
+// the host implementation (csrc/scene/reproject.cpp); taps run in the order
+// (0,0), (1,0), (0,1), (1,1), sums left to right, no atomics, no LDS.
+//
+// A gather-bound streaming kernel: per pixel 32 B of current guide, four taps
+// of 16 B accumulator + 32 B guide that neighbouring pixels share (about 48 B
+// of unique previous-frame traffic under smooth motion), and 16 B written.
+// Guide records are read as the two float4 they are.  Pixels map in 16x16
+// tiles per 256-thread block, like the guide kernel, so a block's taps fall in
+// a compact 17x17 region of the previous image.  A pixel without a history by
+// the projection alone (off frame, behind the previous camera) loads no tap.
+// The four taps are loaded together from coordinates clamped into the
+// previous image, before any of the per-tap decisions.  Measured against a
+// row-major thread mapping, against no early exit, and against a first form
+// that tested each tap before loading it (one dependent load after another,
+// 1.2 x as long): DESIGN.md §6 row 8.
+#include "pt_device.hpp"
+#include "kernels.hpp"
+#include "../../../include/pt_reproject.h"
+
+namespace ptd {
+
+struct reproject_args {
+    pt_packed_camera camera, prev_camera;
+    pt_reproject_parameters params;
+    uint32_t w, h, wp, hp;
+};
+
+PT_DEV pt_denoise_guide ReprojectGuide(float4 ga, float4 gb)
+{
+    pt_denoise_guide g;
+    g.normal[0] = ga.x; g.normal[1] = ga.y; g.normal[2] = ga.z;
+    g.time = ga.w;
+    g.albedo[0] = gb.x; g.albedo[1] = gb.y; g.albedo[2] = gb.z;
+    g.shape = __float_as_uint(gb.w);
+    return g;
+}
+
+__global__ __launch_bounds__(256) void reproject_kernel(const float4* __restrict__ prev,
+                                                        const float4* __restrict__ prev_guides,
+                                                        const float4* __restrict__ guides, reproject_args P,
+                                                        float4* __restrict__ out)
+{
+    const uint32_t x = blockIdx.x * 16 + (threadIdx.x & 15u), y = blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (x >= P.w || y >= P.h) return;
+    const size_t ip = (size_t)y * P.w + x;
+    const pt_denoise_guide gc = ReprojectGuide(guides[2 * ip], guides[2 * ip + 1]);
+    pt_reproject_target T;
+    pt_reproject_sums S{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (pt_reproject_locate(&P.camera, &P.prev_camera, x, y, P.w, P.h, P.wp, P.hp, gc.shape, gc.time, &T)) {
+        // All four taps are loaded first, from coordinates clamped into the
+        // previous image (wp, hp >= 1: always in bounds), so the twelve
+        // loads are in flight together; the decisions follow.
+        float4 c[4], ga[4], gb[4];
+        bool inside[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const int64_t qx = T.x0 + (i & 1), qy = T.y0 + (i >> 1);
+            inside[i] = qx >= 0 && qy >= 0 && qx < (int64_t)P.wp && qy < (int64_t)P.hp;
+            const int64_t cx = qx < 0 ? 0 : (qx >= (int64_t)P.wp ? (int64_t)P.wp - 1 : qx);
+            const int64_t cy = qy < 0 ? 0 : (qy >= (int64_t)P.hp ? (int64_t)P.hp - 1 : qy);
+            const size_t iq = (size_t)cy * P.wp + (size_t)cx;
+            c[i] = prev[iq];
+            ga[i] = prev_guides[2 * iq];
+            gb[i] = prev_guides[2 * iq + 1];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            if (!inside[i]) continue;
+            const float hp[4] = {c[i].x, c[i].y, c[i].z, c[i].w};
+            const pt_denoise_guide gp = ReprojectGuide(ga[i], gb[i]);
+            if (!pt_reproject_tap_valid(&P.params, &T, &gc, hp, &gp)) continue;
+            pt_reproject_add(&S, pt_reproject_tap_weight(&T, i), hp);
+        }
+    }
+    float r[4];
+    pt_reproject_finish(&P.params, &S, r);
+    out[ip] = make_float4(r[0], r[1], r[2], r[3]);
+}
+
+}  // namespace ptd
+
+hipError_t pt_launch_reproject(const float4* prev, const float4* prev_guides, uint32_t wp, uint32_t hp,
+                               const pt_packed_camera* prev_camera, const float4* guides, uint32_t w, uint32_t h,
+                               const pt_packed_camera* camera, const pt_reproject_parameters* p, float4* out,
+                               hipStream_t st)
+{
+    if (w == 0 || h == 0 || wp == 0 || hp == 0) return hipSuccess;
+    ptd::reproject_args P;
+    P.camera = *camera;
+    P.prev_camera = *prev_camera;
+    P.params = *p;
+    P.w = w; P.h = h; P.wp = wp; P.hp = hp;
+    hipLaunchKernelGGL(ptd::reproject_kernel, dim3((w + 15) / 16, (h + 15) / 16), dim3(256), 0, st, prev, prev_guides,
+                       guides, P, out);
+    return hipGetLastError();
+}

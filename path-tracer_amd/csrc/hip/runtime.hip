@@ -10,6 +10,7 @@
 #include "kernels.hpp"
 #include "../../../include/pt_api.h"
 #include "../../../include/pt_denoise.h"
+#include "../../../include/pt_reproject.h"
 
 #include <rccl/rccl.h>
 
@@ -2253,6 +2254,38 @@ int ptDenoiseSampleBufferPair(pt_device* d, pt_sample_buffer* a, pt_sample_buffe
                                       DenoisePairLattice(g->variant, i), image(i + 1), d->stream));
         if (int e = EndTimed(d, ep)) return e;
     }
+    return 0;
+}
+
+// --- temporal reprojection (reproject.hip) ---------------------
+
+int ptReprojectSampleBuffer(pt_device* d, pt_sample_buffer* prev, pt_denoise_guides* pg, const pt_packed_camera* pc,
+                            pt_denoise_guides* g, const pt_packed_camera* c, const pt_reproject_parameters* p,
+                            pt_sample_buffer* dst)
+{
+    if (!d || !prev || !pg || !pc || !g || !c || !p || !dst) { SetError("null argument"); return -1; }
+    if (prev == dst) { SetError("reproject: prev and dst are the same sample buffer"); return -1; }
+    if (pg == g) { SetError("reproject: prev_guides and guides are the same object"); return -1; }
+    if (prev->dev != d || dst->dev != d || pg->dev != d || g->dev != d) {
+        SetError("reproject: objects of another device");
+        return -1;
+    }
+    if (prev->width != pg->width || prev->height != pg->height || dst->width != g->width || dst->height != g->height) {
+        SetError("reproject: size mismatch (prev %ux%u, prev_guides %ux%u, guides %ux%u, dst %ux%u)", prev->width,
+                 prev->height, pg->width, pg->height, g->width, g->height, dst->width, dst->height);
+        return -1;
+    }
+    if (!pt_reproject_parameters_ok(p)) {
+        SetError("reproject: bad parameters (NormalCosine in (-1, 1], DepthTolerance > 0, MinWeight in (0, 1], "
+                 "MaxHistory > 0)");
+        return -1;
+    }
+    PT_HIP(hipSetDevice(d->id));
+    event_pair ep{};
+    if (int e = BeginTimed(d, PT_KERNEL_REPROJECT, ep)) return e;
+    PT_HIP(pt_launch_reproject(prev->accum, pg->records.ptr, pg->width, pg->height, pc, g->records.ptr, g->width,
+                               g->height, c, p, dst->accum, d->stream));
+    if (int e = EndTimed(d, ep)) return e;
     return 0;
 }
 

@@ -100,6 +100,7 @@ class DeviceScene:
     def __init__(self, device: Device):
         L = N.hip_lib()
         self.device = device
+        self.cameras = np.zeros(0, dtype=N.CAMERA_DTYPE)
         self._h = L.ptCreateScene(device.handle)
         if not self._h:
             raise PathTracerError(L.ptGetLastError().decode())
@@ -119,6 +120,11 @@ class DeviceScene:
     def update(self, scene, dirty_flags: int = 0xFFFFFFFF):
         packs = scene.packs() if hasattr(scene, "packs") else scene
         _check(N.hip_lib().ptUpdateScene(self.device.handle, self._h, C.byref(packs), dirty_flags), "ptUpdateScene")
+        # The packed camera records as uploaded (FrameHistory keeps a frame's own).
+        self.cameras = np.zeros(0, dtype=N.CAMERA_DTYPE)
+        if packs.camera_count and packs.cameras:
+            buf = (C.c_char * (packs.camera_count * N.CAMERA_DTYPE.itemsize)).from_address(packs.cameras)
+            self.cameras = np.frombuffer(buf, dtype=N.CAMERA_DTYPE).copy()
 
     @property
     def stack_needed(self) -> int:
@@ -395,6 +401,61 @@ def denoise_pair_host(accum_a: np.ndarray, accum_b: np.ndarray, guides: np.ndarr
     return out
 
 
+class ReprojectParameters:
+    """pt_reproject_parameters (pt_packed.h): which taps of the previous
+    frame still show a pixel's surface (NormalCosine, DepthTolerance), how
+    much valid bilinear weight makes a history (MinWeight) and the cap on the
+    carried sample count (MaxHistory; inf: none).  The defaults are the ones
+    settled on configs 1 and 3 after a small pan, 128 rounds of history and 2
+    or 8 new ones against 4096."""
+
+    def __init__(self, NormalCosine: float = 0.9, DepthTolerance: float = 0.05, MinWeight: float = 0.25,
+                 MaxHistory: float = 64.0):
+        self.NormalCosine, self.DepthTolerance = float(NormalCosine), float(DepthTolerance)
+        self.MinWeight, self.MaxHistory = float(MinWeight), float(MaxHistory)
+
+    def as_struct(self) -> N.pt_reproject_parameters:
+        return N.pt_reproject_parameters(self.NormalCosine, self.DepthTolerance, self.MinWeight, self.MaxHistory)
+
+
+def _camera_struct(camera) -> N.pt_packed_camera:
+    """A packed camera record (scene.arrays()["cameras"][i]) as the C struct."""
+    if isinstance(camera, N.pt_packed_camera):
+        return camera
+    c = np.asarray(camera, dtype=N.CAMERA_DTYPE)
+    if c.shape != ():
+        raise ValueError(f"one camera record expected, got shape {c.shape}")
+    return N.pt_packed_camera.from_buffer_copy(c.tobytes())
+
+
+def reproject_host(prev_accum: np.ndarray, prev_guides: np.ndarray, prev_camera, guides: np.ndarray, camera,
+                   params: "ReprojectParameters | None" = None) -> np.ndarray:
+    """Temporal reprojection on the CPU (ptsReproject, libptscene.so), which
+    the device kernel equals bit for bit.  prev_accum: (Hp, Wp, 4) accumulator
+    of the previous view; prev_guides: its (Hp, Wp) DENOISE_GUIDE_DTYPE
+    records; guides: the current view's (H, W) records; prev_camera, camera:
+    the packed camera records (scene.arrays()["cameras"][i]) the two guide
+    images were rendered with.  Returns (H, W, 4): (mean XYZ * n, n) with n
+    the carried sample count, zeros where the pixel has no history."""
+    a = np.ascontiguousarray(prev_accum, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"accumulator of shape {a.shape}, expected (H, W, 4)")
+    pg = np.ascontiguousarray(prev_guides, dtype=N.DENOISE_GUIDE_DTYPE)
+    if pg.shape != a.shape[:2]:
+        raise ValueError(f"previous guides of shape {pg.shape}, accumulator {a.shape[:2]}")
+    g = np.ascontiguousarray(guides, dtype=N.DENOISE_GUIDE_DTYPE)
+    if g.ndim != 2:
+        raise ValueError(f"guides of shape {g.shape}, expected (H, W)")
+    out = np.zeros(g.shape + (4,), np.float32)
+    pc, c = _camera_struct(prev_camera), _camera_struct(camera)
+    p = (params or ReprojectParameters()).as_struct()
+    rc = N.scene_lib().ptsReproject(a.shape[1], a.shape[0], N.fptr(a), pg.ctypes.data, C.byref(pc), g.shape[1],
+                                    g.shape[0], g.ctypes.data, C.byref(c), C.byref(p), N.fptr(out))
+    if rc != 0:
+        raise PathTracerError(f"ptsReproject: bad arguments (status {rc})")
+    return out
+
+
 class DenoiseGuides:
     """Per-pixel primary-hit records of the scene camera's central rays
     (normal, hit time, base colour, shape) that steer the denoiser, plus the
@@ -506,6 +567,28 @@ class SampleBuffer:
             raise
         return dst
 
+    def reproject(self, prev_guides: "DenoiseGuides", prev_camera, guides: "DenoiseGuides", camera,
+                  params: "ReprojectParameters | None" = None, out: "SampleBuffer | None" = None) -> "SampleBuffer":
+        """Temporal reprojection on the device (ptReprojectSampleBuffer;
+        enqueues): this buffer is the previous view's accumulator, prev_guides
+        and prev_camera its guides and packed camera record, guides and camera
+        the current view's.  `out` (a new sample buffer of the guides' size
+        when None) receives (mean XYZ * n, n) per pixel, zeros where the pixel
+        is disoccluded; a renderer with RENDER_FLAG_ACCUMULATE adds its
+        samples on top.  This buffer and both guides are not written."""
+        dst = out if out is not None else SampleBuffer(self.device, guides.width, guides.height)
+        pc, c = _camera_struct(prev_camera), _camera_struct(camera)
+        p = (params or ReprojectParameters()).as_struct()
+        try:
+            _check(N.hip_lib().ptReprojectSampleBuffer(self.device.handle, self._h, prev_guides.handle, C.byref(pc),
+                                                       guides.handle, C.byref(c), C.byref(p), dst.handle),
+                   "ptReprojectSampleBuffer")
+        except PathTracerError:
+            if out is None:
+                dst.close()
+            raise
+        return dst
+
     def statistics(self, other: "SampleBuffer | None" = None) -> FrameStatistics:
         """Frame statistics on the device (ptComputeFrameStatistics; blocks):
         of this buffer, or, with `other` (an independent render of the same
@@ -541,6 +624,53 @@ class SampleBuffer:
         if self._h:
             N.hip_lib().ptDestroySampleBuffer(self.device.handle, self._h)
             self._h = None
+
+
+class FrameHistory:
+    """Keeps the last frame (its sample buffer, guides and camera record) so
+    that the next one starts from it: begin_frame() renders the new view's
+    guides and reprojects the stored frame into the new sample buffer.  Thin
+    glue over DenoiseGuides.render and SampleBuffer.reproject."""
+
+    def __init__(self, device: "Device", width: int, height: int, params: "ReprojectParameters | None" = None):
+        self.device = device
+        self.width, self.height = int(width), int(height)
+        self.params = params
+        self._spare = DenoiseGuides(device, self.width, self.height)
+        self.guides = None          # the current frame's guides (after begin_frame)
+        self.buffer = None          # the sample buffer passed to the last begin_frame (non-owning)
+        self.camera = None          # its packed camera record
+
+    def begin_frame(self, ds: "DeviceScene", camera_index: int, sample_buffer: "SampleBuffer") -> bool:
+        """Call after ds.update(scene) and after the frame's renderer.reset()
+        (a Reset clears its sample buffer, pixel by pixel, as the reference's
+        restart does), before its run(): the new rounds then accumulate on
+        top of the history.  sample_buffer is of this history's size and not
+        the last call's buffer.  True: it now holds the reprojected history;
+        False (first call): it was left as it is.  The buffer passed here
+        must stay alive until the next call, which reads what the renderer
+        has accumulated in it by then."""
+        if sample_buffer.width != self.width or sample_buffer.height != self.height:
+            raise ValueError(f"sample buffer {sample_buffer.width}x{sample_buffer.height}, history "
+                             f"{self.width}x{self.height}")
+        camera = ds.cameras[int(camera_index)].copy()
+        guides = self._spare
+        guides.render(ds, camera_index)
+        carried = self.buffer is not None
+        if carried:
+            self.buffer.reproject(self.guides, self.camera, guides, camera, self.params, out=sample_buffer)
+        if self.guides is None:
+            self._spare = DenoiseGuides(self.device, self.width, self.height)
+        else:
+            self._spare = self.guides
+        self.guides, self.buffer, self.camera = guides, sample_buffer, camera
+        return carried
+
+    def close(self):
+        for g in (self._spare, self.guides):
+            if g is not None:
+                g.close()
+        self._spare = self.guides = self.buffer = None
 
 
 class BasicRenderer:

@@ -21,11 +21,17 @@
   shortcut, on C3's accumulator after 8 rounds and on a constant image, with
   ptRenderSampleBuffer and ptAccumulateSampleBuffer on the same buffers, at
   1920x1080 and 3840x2160; every figure three times, to show the spread.
+* reproject (ptReprojectSampleBuffer, reproject.hip):
+  kernel ms of the reprojection launch after a small pan of C3's camera and
+  with the previous camera turned away (no pixel has a history, so every
+  thread leaves before its tap loads), GB/s against the 96 B/pixel estimate, with
+  ptRenderSampleBuffer and one a-trous iteration on the same buffers, at
+  1920x1080 and 3840x2160; every figure three times.
 * host builds (§8(f) row 3): mesh BVH build of a 1.96 M-face mesh on 1 and
   on all of the job's threads, and the RGB -> spectrum table.
 
 Kernel times are HIP events on the device stream (ptGetKernelStats).
-Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|preview|openpbr|host ...]
+Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|reproject|preview|openpbr|host ...]
 (default: all).
 """
 import json
@@ -45,6 +51,7 @@ HBM_GBPS = 8000.0
 K_RESOLVE, K_PREVIEW, K_EXTEND, K_SHADE, K_ROUND = 3, 4, 1, 2, 5
 K_DENOISE, K_GUIDES = 7, 8
 K_STATS = 9
+K_REPROJECT = 10
 
 
 def timed(dev, kernel, fn, reps):
@@ -201,6 +208,66 @@ def stats(pt, dev):
     return out
 
 
+C3_POSE = ((0.75, -0.75, 0.75), (np.pi / 2 - 0.35, 0.0, np.pi / 4))       # configs.cpp
+
+
+def reproject(pt, dev):
+    """Per size, {pan|away}_ms: the reprojection kernel after a small pan
+    of C3's camera (history of 8 rounds) and with the previous camera turned
+    round; pan_gbps: 96 B per pixel over that
+    time; resolve_ms and denoise_step1_ms: the yardsticks on the same
+    buffers; pan_carried: the share of pixels with a history.  Each time is
+    a list: the mean of 10 timed calls after a warm-up call, taken three
+    times in turn."""
+    out = {}
+    scene = pt.Scene.config(3)
+    cam = scene.find_camera(0)
+    ds = pt.DeviceScene(dev)
+    (px, py, pz), (rx, ry, rz) = C3_POSE
+    for W, H in ((1920, 1080), (3840, 2160)):
+        scene.move_camera(cam, position=(px, py, pz), rotation=(rx, ry, rz))
+        scene.pack()
+        ds.update(scene)
+        prev_cam = ds.cameras[0].copy()
+        prev, dst = pt.SampleBuffer(dev, W, H), pt.SampleBuffer(dev, W, H)
+        r = pt.BasicRenderer(dev, ds, prev)
+        r.RenderFlags = 3
+        r.reset()
+        r.run(8)
+        prev_guides, guides = pt.DenoiseGuides(dev, W, H), pt.DenoiseGuides(dev, W, H)
+        prev_guides.render(ds, 0)
+        scene.move_camera(cam, position=(px + 0.02, py + 0.02, pz), rotation=(rx, ry, rz + 0.02))
+        scene.pack()
+        ds.update(scene)
+        now_cam = ds.cameras[0].copy()
+        guides.render(ds, 0)
+        scene.move_camera(cam, position=(px, py, pz), rotation=(rx, ry, rz + np.pi))
+        scene.pack()
+        away_cam = scene.arrays()["cameras"][0].copy()
+        runs = {"resolve_ms": (K_RESOLVE, lambda: prev.render(ToneMappingMode=pt.TONE_MAPPING_ACES)),
+                "denoise_step1_ms": (K_DENOISE, lambda: prev.denoise(prev_guides, pt.DenoiseParameters(Iterations=1),
+                                                                     out=dst))}
+        for move, pc in (("pan", prev_cam), ("away", away_cam)):
+            runs[f"{move}_ms"] = (K_REPROJECT, lambda pc=pc: prev.reproject(prev_guides, pc, guides, now_cam, out=dst))
+        res = {"pixels": W * H}
+        for key in runs:
+            res[key] = []
+        for _ in range(3):
+            for key, (kernel, fn) in runs.items():
+                fn()   # warm
+                ms, _ = timed(dev, kernel, fn, 10)
+                res[key].append(round(ms, 4))
+        res["pan_gbps"] = [round(96.0 * W * H / (ms * 1e-3) / 1e9, 1) for ms in res["pan_ms"]]
+        prev.reproject(prev_guides, prev_cam, guides, now_cam, out=dst)
+        res["pan_carried"] = round(dst.statistics().filled / (W * H), 4)
+        out[f"{W}x{H}"] = res
+        for x in (guides, prev_guides, r, dst, prev):
+            x.close()
+    ds.close()
+    scene.close()
+    return out
+
+
 def preview(pt, dev):
     out = {}
     modes = {"base_color": pt.PREVIEW_RENDER_MODE_BASE_COLOR, "shaded": pt.PREVIEW_RENDER_MODE_BASE_COLOR_SHADED,
@@ -280,7 +347,7 @@ def host_builds(pt):
 
 def main():
     pt = load()
-    entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "preview": preview, "openpbr": openpbr}
+    entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "reproject": reproject, "preview": preview, "openpbr": openpbr}
     want = sys.argv[1:] or list(entries) + ["host"]
     dev = pt.Device(0)
     res = {name: fn(pt, dev) for name, fn in entries.items() if name in want}

@@ -38,6 +38,7 @@ run asan_scenes "$A" scene $(ls -d "$C"/scenes/s*/ | sed 's|$|scene.json|') "$C/
 run asan_render "$A" render
 run asan_denoise "$A" denoise
 run asan_stats "$A" stats
+run asan_reproject "$A" reproject
 PT_BVH_THREADS=8 run tsan_bvh "$T" bvh 300000
 run tsan_render "$T" render
 PT_BVH_THREADS=8 run asan_bvh "$A" bvh 200000

@@ -21,12 +21,19 @@
 //                               small random, empty and NaN / inf / denormal
 //                               images, single and pair, one pixel included;
 //                               rejected arguments
+//   san_driver reproject        ptsReproject and ptsCentralCameraRay on random
+//                               small frames (1x1 and differing previous and
+//                               current sizes included) under cameras of every
+//                               model that project inside, far outside, behind
+//                               and to non-finite positions, with random,
+//                               empty and NaN / inf histories; rejected arguments
 #include "../../path-tracer_amd/csrc/scene/scene.hpp"
 #include "../../path-tracer_amd/csrc/scene/configs.hpp"
 #include "../../path-tracer_amd/csrc/scene/image.hpp"
 #include "../../oracle/pt_oracle.h"
 #include "../../include/pt_scene.h"
 
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <random>
@@ -275,9 +282,117 @@ static int Stats()
     return bad != 0;
 }
 
+// A camera record at `pos`, turned by `yaw` about z from the configs' forward
+// direction (+y); To = T R, From = R^-1 T^-1, column-major.
+static pt_packed_camera SanCamera(uint32_t model, const float pos[3], float yaw)
+{
+    pt_packed_camera c{};
+    c.Model = model;
+    c.FocalLength = 0.05f;
+    c.SensorDistance = 0.0508f;
+    c.SensorSize[0] = 0.032f;
+    c.SensorSize[1] = 0.016f;
+    const float cs = std::cos(yaw), sn = std::sin(yaw);
+    // camera axes in the world: x' = (cs, sn, 0), y' = (0, 0, 1), z' = x' cross y' (the camera looks along -z')
+    const float X[3] = {cs, sn, 0.0f}, Y[3] = {0.0f, 0.0f, 1.0f}, Z[3] = {sn, -cs, 0.0f};
+    float* To = c.Transform.To;
+    float* From = c.Transform.From;
+    for (int r = 0; r < 3; r++) {
+        To[0 + r] = X[r]; To[4 + r] = Y[r]; To[8 + r] = Z[r]; To[12 + r] = pos[r];
+        From[4 * r + 0] = X[r]; From[4 * r + 1] = Y[r]; From[4 * r + 2] = Z[r];
+    }
+    To[15] = From[15] = 1.0f;
+    for (int r = 0; r < 3; r++) {
+        const float* A = r == 0 ? X : (r == 1 ? Y : Z);
+        From[12 + r] = -(A[0] * pos[0] + A[1] * pos[1] + A[2] * pos[2]);
+    }
+    return c;
+}
+
+static int Reproject()
+{
+    std::mt19937 rng(13);
+    std::uniform_real_distribution<float> u(0.0f, 4.0f), s(-1.0f, 1.0f);
+    const float nan = std::nanf(""), inf = HUGE_VALF;
+    const float odd[] = {0.0f, -0.0f, -1.0f, nan, inf, -inf, 1e-45f, 1e-38f, 3e38f, 1.0f};
+    const uint32_t sizes[][4] = {{1, 1, 1, 1}, {1, 1, 5, 3}, {7, 1, 1, 9}, {3, 2, 3, 2}, {16, 16, 16, 16},
+                                 {29, 33, 37, 21}, {64, 32, 37, 21}, {17, 33, 40, 24}};
+    const float origin[3] = {0.0f, -4.0f, 1.0f}, aside[3] = {0.4f, -4.0f, 1.0f}, far_away[3] = {1e30f, -4.0f, 1.0f},
+                nowhere[3] = {nan, inf, 0.0f};
+    int bad = 0;
+    for (auto& z : sizes) {
+        const uint32_t Wp = z[0], Hp = z[1], W = z[2], H = z[3];
+        const size_t np = (size_t)Wp * Hp, n = (size_t)W * H;
+        for (uint32_t model = 0; model < 4; model++) {       // 3: an unknown model
+            // the previous camera: a small move, turned away, far outside, non-finite, a zero matrix
+            pt_packed_camera prev[6] = {SanCamera(model, aside, 0.1f), SanCamera(model, origin, 3.14159265f),
+                                        SanCamera(model, origin, 1.2f), SanCamera(model, far_away, 0.0f),
+                                        SanCamera(model, nowhere, nan), SanCamera(model, origin, 0.0f)};
+            std::memset(&prev[5].Transform, 0, sizeof(prev[5].Transform));
+            const pt_packed_camera cur = SanCamera(model == 3 ? 0 : model, origin, 0.0f);
+            for (int pc = 0; pc < 6; pc++) {
+                for (int kind = 0; kind < 3; kind++) {        // history: random, empty, odd values
+                    std::vector<float> acc(4 * np), out(4 * n, -1.0f);
+                    std::vector<pt_denoise_guide> gp(np), gc(n);
+                    for (size_t i = 0; i < 4 * np; i++)
+                        acc[i] = kind == 0 ? (i % 4 == 3 ? (float)(rng() % 5) : u(rng))
+                                           : (kind == 1 ? 0.0f : odd[rng() % (sizeof(odd) / sizeof(odd[0]))]);
+                    for (std::vector<pt_denoise_guide>* g : {&gp, &gc}) {
+                        for (pt_denoise_guide& r : *g) {
+                            for (int k = 0; k < 3; k++) { r.normal[k] = s(rng); r.albedo[k] = 0.5f * u(rng); }
+                            r.time = rng() % 16 == 0 ? odd[rng() % (sizeof(odd) / sizeof(odd[0]))] : 1.0f + u(rng);
+                            r.shape = rng() % 4 == 0 ? 0xFFFFFFFFu : rng() % 3;
+                        }
+                    }
+                    pt_reproject_parameters p{0.5f, 0.5f, 0.25f, kind == 2 ? inf : 8.0f};
+                    if (ptsReproject(Wp, Hp, acc.data(), gp.data(), &prev[pc], W, H, gc.data(), &cur, &p, out.data()) != 0) {
+                        std::printf("reproject: failed\n");
+                        return 1;
+                    }
+                    size_t carried = 0;
+                    for (size_t i = 0; i < n; i++) {
+                        carried += out[4 * i + 3] > 0.0f;
+                        bad += !(out[4 * i + 3] >= 0.0f);                       // a count, never NaN or negative
+                        bad += kind != 2 && out[4 * i + 3] > 8.0f;             // capped
+                    }
+                    bad += kind == 1 && carried != 0;                            // an empty history carries nothing
+                    bad += (model == 3 || pc == 4 || pc == 5) && carried != 0;   // no projection: no history
+                    std::printf("reproject %ux%u -> %ux%u model %u prev %d history %d: %zu of %zu pixels\n", Wp, Hp, W,
+                                H, model, pc, kind, carried, n);
+                }
+            }
+            float o[3], v[3];
+            for (uint32_t y = 0; y < H; y++)
+                for (uint32_t x = 0; x < W; x++) bad += (ptsCentralCameraRay(&cur, x, y, W, H, o, v) != 0);
+            bad += ptsCentralCameraRay(&prev[4], 0, 0, W, H, o, v) != (model == 3 ? -1 : 0);
+        }
+    }
+    // rejected arguments leave `out` untouched
+    float acc[4] = {1, 1, 1, 1}, out[4] = {7, 7, 7, 7};
+    pt_denoise_guide gp{}, gc{};
+    const pt_packed_camera cam = SanCamera(0, origin, 0.0f);
+    pt_reproject_parameters ok{0.9f, 0.05f, 0.25f, 64.0f}, cosine{-1.0f, 0.02f, 0.25f, 64.0f}, depth{0.9f, 0.0f, 0.25f, 64.0f},
+        weight{0.9f, 0.02f, 1.5f, 64.0f}, cap{0.9f, 0.02f, 0.25f, nan};
+    bad += ptsReproject(1, 1, nullptr, &gp, &cam, 1, 1, &gc, &cam, &ok, out) == 0;
+    bad += ptsReproject(1, 1, acc, nullptr, &cam, 1, 1, &gc, &cam, &ok, out) == 0;
+    bad += ptsReproject(1, 1, acc, &gp, nullptr, 1, 1, &gc, &cam, &ok, out) == 0;
+    bad += ptsReproject(1, 1, acc, &gp, &cam, 1, 1, nullptr, &cam, &ok, out) == 0;
+    bad += ptsReproject(1, 1, acc, &gp, &cam, 1, 1, &gc, nullptr, &ok, out) == 0;
+    bad += ptsReproject(1, 1, acc, &gp, &cam, 1, 1, &gc, &cam, nullptr, out) == 0;
+    bad += ptsReproject(1, 1, acc, &gp, &cam, 1, 1, &gc, &cam, &ok, nullptr) == 0;
+    bad += ptsReproject(1, 1, acc, &gp, &cam, 1, 1, &gp, &cam, &ok, out) == 0;
+    bad += ptsReproject(0, 1, acc, &gp, &cam, 1, 1, &gc, &cam, &ok, out) == 0;
+    bad += ptsReproject(1, 1, acc, &gp, &cam, 1, 0, &gc, &cam, &ok, out) == 0;
+    for (pt_reproject_parameters* p : {&cosine, &depth, &weight, &cap})
+        bad += ptsReproject(1, 1, acc, &gp, &cam, 1, 1, &gc, &cam, p, out) == 0;
+    for (float v : out) bad += v != 7.0f;
+    std::printf("reproject: %d checks wrong\n", bad);
+    return bad != 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise|stats ...\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise|stats|reproject ...\n"); return 2; }
     std::string cmd = argv[1];
     if (cmd == "decode") return Decode(argc - 2, argv + 2);
     if (cmd == "model") return Model(argc - 2, argv + 2);
@@ -286,6 +401,7 @@ int main(int argc, char** argv)
     if (cmd == "bvh") return Bvh(argc > 2 ? (uint32_t)std::strtoul(argv[2], nullptr, 10) : 200000u);
     if (cmd == "denoise") return Denoise();
     if (cmd == "stats") return Stats();
+    if (cmd == "reproject") return Reproject();
     std::fprintf(stderr, "unknown command %s\n", cmd.c_str());
     return 2;
 }
