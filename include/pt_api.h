@@ -33,7 +33,8 @@
  * two half renders), a variance-guided form of the denoiser that takes
  * those two half renders (ptDenoiseSampleBufferPair), and temporal
  * reprojection of an accumulator into a new view (ptReprojectSampleBuffer),
- * which keeps a frame's history across a camera move.
+ * which keeps a frame's history across a camera move
+ * (ptReprojectSampleBufferMoving: and across an object move).
  *
  * Conventions: creators return NULL on failure and set ptGetLastError();
  * other calls return 0 on success or a non-zero status (HIP / RCCL error
@@ -108,7 +109,7 @@ enum {
     PT_KERNEL_DENOISE = 7,   /* one a-trous iteration of ptDenoiseSampleBuffer */
     PT_KERNEL_GUIDES  = 8,   /* ptRenderDenoiseGuides */
     PT_KERNEL_STATS   = 9,   /* ptComputeFrameStatistics' pass and ptAccumulateSampleBuffer's add */
-    PT_KERNEL_REPROJECT = 10, /* ptReprojectSampleBuffer */
+    PT_KERNEL_REPROJECT = 10, /* ptReprojectSampleBuffer, ptReprojectSampleBufferMoving */
     PT_KERNEL_COUNT   = 11,
 };
 
@@ -461,6 +462,26 @@ int  ptReprojectSampleBuffer(pt_device* device, pt_sample_buffer* prev, pt_denoi
                              const pt_packed_camera* prev_camera, pt_denoise_guides* guides,
                              const pt_packed_camera* camera, const pt_reproject_parameters* params,
                              pt_sample_buffer* dst);
+/* The same across an object move: motion is a table of
+ * motion_count records in host memory, one per packed shape (ptsShapeMotion,
+ * pt_scene.h, fills it from the two frames' packed shapes).  A hit pixel
+ * whose shape's record is PT_SHAPE_MOTION_MOVED looks for its history where
+ * that surface point was in the previous frame and expects the normal the
+ * shape had there; a shape index >= motion_count or a NO_HISTORY record
+ * gives the pixel no history; every other pixel gets
+ * ptReprojectSampleBuffer's bits.  The table is read during the call (into a
+ * pinned copy) and uploaded, in stream order, into a buffer the device object
+ * owns (grown on demand); then one launch (PT_KERNEL_REPROJECT).  A call waits
+ * for the previous call's upload, not for its kernel.  motion == NULL with
+ * motion_count == 0 means no table: ptReprojectSampleBuffer itself.  Equals
+ * ptsReprojectMoving bit for bit.  Fails, launching and writing nothing, on
+ * ptReprojectSampleBuffer's errors and on motion == NULL with
+ * motion_count > 0. */
+int  ptReprojectSampleBufferMoving(pt_device* device, pt_sample_buffer* prev, pt_denoise_guides* prev_guides,
+                                   const pt_packed_camera* prev_camera, pt_denoise_guides* guides,
+                                   const pt_packed_camera* camera, const pt_shape_motion* motion,
+                                   uint32_t motion_count, const pt_reproject_parameters* params,
+                                   pt_sample_buffer* dst);
 
 /* Frame statistics (no reference counterpart; definition, kernel design and
  * measured times in DESIGN.md §6 row 6; helpers that read the result in

@@ -232,6 +232,22 @@ typedef struct pt_reproject_parameters {
     float    MaxHistory;               /* > 0, default 64 (+inf: none): cap on the carried sample count */
 } pt_reproject_parameters;
 
+/* One shape's motion between two packed scenes, filled
+ * by ptsShapeMotion (pt_scene.h) and read by the moving-shape reprojection
+ * (pt_reproject.h).  Point: rows 0..2 of the affine map from the current
+ * world to the previous one (To_prev From_cur), row-major, Point[4r + c].
+ * Normal: takes a current world normal into the previous world frame, before
+ * normalisation (the inverse transpose of Point's linear part), Normal[3r + c]. */
+#define PT_SHAPE_MOTION_MOVED      1u  /* the transform changed: Point and Normal hold the motion */
+#define PT_SHAPE_MOTION_NO_HISTORY 2u  /* another or a new shape, or a non-finite transform: matrices are zero */
+
+typedef struct pt_shape_motion {
+    float    Point[12];
+    float    Normal[9];
+    uint32_t Flags;                    /* 0: unmoved (identity matrices, row 8's path) */
+    uint32_t Pad0[2];
+} pt_shape_motion;
+
 /* Frame statistics (no reference counterpart; definition in DESIGN.md §6 row
  * 6, arithmetic in pt_stats.h): integer counts and float min/max of one
  * accumulator, or of the sum A + B of two with the noise fields taken from
@@ -261,6 +277,7 @@ static_assert(sizeof(pt_denoise_guide) == 32, "denoise_guide");
 static_assert(sizeof(pt_denoise_parameters) == 20, "denoise_parameters");
 static_assert(sizeof(pt_denoise_pair_parameters) == 20, "denoise_pair_parameters");
 static_assert(sizeof(pt_reproject_parameters) == 16, "reproject_parameters");
+static_assert(sizeof(pt_shape_motion) == 96, "shape_motion");
 static_assert(sizeof(pt_packed_transform) == 128, "packed_transform");
 static_assert(sizeof(pt_packed_texture) == 32, "packed_texture");
 static_assert(sizeof(pt_packed_shape) == 144, "packed_shape");

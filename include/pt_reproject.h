@@ -1,6 +1,7 @@
 /*
  * pt_reproject.h — temporal reprojection of an accumulator into a new view
- * (definition in DESIGN.md §6 row 8), written once for the device kernel
+ * (definition in DESIGN.md §6 row 8; row 9, which follows moved shapes, at the
+ * end), written once for the device kernel
  * (csrc/hip/reproject.hip) and the host implementation
  * (csrc/scene/reproject.cpp) under pt_fp.h's convention: IEEE binary32, no
  * contraction, sums left to right, pt_sin / pt_cos / pt_atan2 / pt_asin /
@@ -210,6 +211,77 @@ PT_HD void pt_reproject_finish(const pt_reproject_parameters* p, const pt_reproj
     out[1] = (S->y / S->w) * n;
     out[2] = (S->z / S->w) * n;
     out[3] = n;
+}
+
+/* --- Row 9: reprojection that follows moved shapes ---------------------------
+ *
+ * Everything above holds, except for a hit pixel whose guide shape s has a
+ * motion record (pt_shape_motion, pt_packed.h; ptsShapeMotion fills a table
+ * of them from two packed scenes).  What a pixel does with its shape: */
+enum {
+    PT_REPROJECT_MOTION_STATIC = 0,   /* a miss, or Flags without either bit: row 8, same operations, same bits */
+    PT_REPROJECT_MOTION_MOVED  = 1,   /* the record's Point and Normal are applied */
+    PT_REPROJECT_MOTION_NONE   = 2,   /* s >= motion_count or PT_SHAPE_MOTION_NO_HISTORY: no history */
+};
+
+/* From the record's Flags alone (NO_HISTORY wins over MOVED; other bits are
+ * ignored).  The caller has checked shape != PT_SHAPE_INDEX_NONE and
+ * shape < motion_count. */
+PT_HD int pt_reproject_motion_kind(uint32_t Flags)
+{
+    if (Flags & PT_SHAPE_MOTION_NO_HISTORY) return PT_REPROJECT_MOTION_NONE;
+    return (Flags & PT_SHAPE_MOTION_MOVED) ? PT_REPROJECT_MOTION_MOVED : PT_REPROJECT_MOTION_STATIC;
+}
+
+/* Steps 1-3 for a hit pixel of a moved shape.  P as in row 8; Pp = Point (P, 1)
+ * is where that surface point was in the previous world; the previous view
+ * is asked for Pp, and dist is Pp's distance from the previous ray origin.
+ * *Ne: the normal the previous guide should show, normalize(Normal n) with
+ * the rows summed left to right.  0: no history (as pt_reproject_locate, or
+ * a normal whose image has a squared length that is not > 0 or not finite). */
+PT_HD int pt_reproject_locate_moved(const pt_packed_camera* Cc, const pt_packed_camera* Cp, uint32_t x, uint32_t y,
+                                    uint32_t w, uint32_t h, uint32_t wp, uint32_t hp, const float* normal, float time,
+                                    const float* Point, const float* Normal, pt_reproject_target* T, pt3* Ne)
+{
+    if (!pt_reproject_camera_ok(Cc) || !pt_reproject_camera_ok(Cp)) return 0;
+    pt3 O, V;
+    pt_reproject_central_ray(Cc, x, y, w, h, &O, &V);
+    pt3 P = v3(O.x + V.x * time, O.y + V.y * time, O.z + V.z * time);
+    pt3 Pp = v3(((Point[0] * P.x + Point[1] * P.y) + Point[2] * P.z) + Point[3],
+                ((Point[4] * P.x + Point[5] * P.y) + Point[6] * P.z) + Point[7],
+                ((Point[8] * P.x + Point[9] * P.y) + Point[10] * P.z) + Point[11]);
+    pt3 L = mat4_mul_point(Cp->Transform.From, Pp);
+    T->dist = length(Pp - mat4_mul_point(Cp->Transform.To, v3s(0)));
+    pt3 N = v3((Normal[0] * normal[0] + Normal[1] * normal[1]) + Normal[2] * normal[2],
+               (Normal[3] * normal[0] + Normal[4] * normal[1]) + Normal[5] * normal[2],
+               (Normal[6] * normal[0] + Normal[7] * normal[1]) + Normal[8] * normal[2]);
+    float q = dot(N, N);
+    if (!(q > 0.0f) || !pt_reproject_finite(q)) return 0;
+    *Ne = N * (1.0f / pt_sqrt(q));
+    float Nx, Ny;
+    if (!pt_reproject_project(Cp, L, &Nx, &Ny)) return 0;
+    float u = Nx * (float)wp - 0.5f, v = Ny * (float)hp - 0.5f;
+    if (!(u > -1.0f && u < (float)wp && v > -1.0f && v < (float)hp)) return 0;
+    float fu = pt_floor(u), fv = pt_floor(v);
+    T->x0 = (int64_t)fu;
+    T->y0 = (int64_t)fv;
+    T->fx = u - fu;
+    T->fy = v - fv;
+    return 1;
+}
+
+/* Step 4 for a tap of a moved shape's pixel: pt_reproject_tap_valid with the
+ * expected normal Ne in the current normal's place. */
+PT_HD int pt_reproject_tap_valid_moved(const pt_reproject_parameters* p, const pt_reproject_target* T, uint32_t shape,
+                                       pt3 Ne, const float* hp, const pt_denoise_guide* gp)
+{
+    if (!(pt_reproject_finite(hp[0]) && pt_reproject_finite(hp[1]) && pt_reproject_finite(hp[2]) &&
+          pt_reproject_finite(hp[3]) && hp[3] > 0.0f))
+        return 0;
+    if (gp->shape != shape) return 0;
+    float d = (gp->normal[0] * Ne.x + gp->normal[1] * Ne.y) + gp->normal[2] * Ne.z;
+    if (!(d >= p->NormalCosine)) return 0;
+    return pt_abs(gp->time - T->dist) <= p->DepthTolerance * T->dist;
 }
 
 #endif /* PT_REPROJECT_H */

@@ -202,6 +202,39 @@ int  ptsReproject(uint32_t prev_width, uint32_t prev_height, const float* prev_a
                   const pt_denoise_guide* prev_guides, const pt_packed_camera* prev_camera, uint32_t width,
                   uint32_t height, const pt_denoise_guide* guides, const pt_packed_camera* camera,
                   const pt_reproject_parameters* params, float* out_rgba);
+/* The motion table of the moving-shape reprojection:
+ * out[i], i < count, is shape i's motion between two packs of one scene,
+ * prev_shapes (prev_count records) and shapes (count records), in binary32
+ * without contraction, matrices column-major as everywhere.
+ *   - i >= prev_count, another Type, another MeshRootNodeIndex, or a
+ *     non-finite value in either Transform: Flags = PT_SHAPE_MOTION_NO_HISTORY,
+ *     zero matrices;
+ *   - the two 128-byte Transform records bytewise equal: Flags = 0, identity
+ *     matrices (the pixel takes row 8's path and gets row 8's bits);
+ *   - otherwise Flags = PT_SHAPE_MOTION_MOVED, Point = rows 0..2 of
+ *     To_prev From_cur, Normal = the transpose of the linear part of
+ *     To_cur From_prev (the inverse transpose of Point's linear part; no
+ *     inverse is computed).
+ * Shapes are matched by their index in the packed array: the caller
+ * guarantees that the set of entities, and so their order, is the same in
+ * both packs.  After an entity was added or removed the indices shift and
+ * the table is wrong without any flag showing it; only the indices beyond
+ * prev_count are NO_HISTORY.  Non-zero on a NULL array with a non-zero count. */
+int  ptsShapeMotion(const pt_packed_shape* prev_shapes, uint32_t prev_count, const pt_packed_shape* shapes,
+                    uint32_t count, pt_shape_motion* out);
+/* ptsReproject with a motion table (ptsShapeMotion): a
+ * hit pixel whose shape's record is MOVED looks for its history where that
+ * surface point was, and expects the normal the shape had there; a shape
+ * index >= motion_count or a NO_HISTORY record gives no history; everything
+ * else is ptsReproject, bit for bit.  motion == NULL with motion_count == 0:
+ * no table, ptsReproject itself.  Equals ptReprojectSampleBufferMoving
+ * (pt_api.h) bit for bit.  Non-zero, leaving out_rgba untouched, on
+ * ptsReproject's errors and on motion == NULL with motion_count > 0. */
+int  ptsReprojectMoving(uint32_t prev_width, uint32_t prev_height, const float* prev_accum,
+                        const pt_denoise_guide* prev_guides, const pt_packed_camera* prev_camera, uint32_t width,
+                        uint32_t height, const pt_denoise_guide* guides, const pt_packed_camera* camera,
+                        const pt_shape_motion* motion, uint32_t motion_count, const pt_reproject_parameters* params,
+                        float* out_rgba);
 /* pt_reproject.h's central camera ray of pixel (x, y) of a width x height
  * frame (the guide kernel's ray: pixel centre, lens centre, the velocity
  * after its packed round trip).  Non-zero on a NULL argument, an empty frame

@@ -217,6 +217,11 @@ GLOBALS_DTYPE = np.dtype([("SkyboxMeanDirection", "<f4", (3,)), ("SkyboxConcentr
 assert SHAPE_NODE_DTYPE.itemsize == 32 and MESH_NODE_DTYPE.itemsize == 32 and MESH_FACE_DTYPE.itemsize == 48
 assert SHAPE_DTYPE.itemsize == 144 and CAMERA_DTYPE.itemsize == 160 and GLOBALS_DTYPE.itemsize == 48
 assert TEXTURE_DTYPE.itemsize == 32
+# pt_shape_motion (include/pt_packed.h): one shape's motion between two packed scenes (ptsShapeMotion).
+SHAPE_MOTION_DTYPE = np.dtype([("Point", "<f4", (12,)), ("Normal", "<f4", (9,)), ("Flags", "<u4"),
+                               ("Pad0", "<u4", (2,))])
+assert SHAPE_MOTION_DTYPE.itemsize == 96
+SHAPE_MOTION_MOVED, SHAPE_MOTION_NO_HISTORY = 1, 2
 
 KERNEL_RAYGEN, KERNEL_EXTEND, KERNEL_SHADE, KERNEL_RESOLVE = 0, 1, 2, 3
 TONE_MAPPING_CLAMP, TONE_MAPPING_REINHARD, TONE_MAPPING_HABLE, TONE_MAPPING_ACES = 0, 1, 2, 3
@@ -233,7 +238,7 @@ DENOISE_MAX_ITERATIONS = 8
 DENOISE_VARIANT_AUTO, DENOISE_VARIANT_GATHER, DENOISE_VARIANT_LATTICE = 0, 1, 2
 KERNEL_STATS = 9     # the frame statistics pass and the sample-buffer add (PT_KERNEL_STATS)
 STATS_VARIANT_AUTO, STATS_VARIANT_PLAIN, STATS_VARIANT_UNIFORM = 0, 1, 2
-KERNEL_REPROJECT = 10   # ptReprojectSampleBuffer (PT_KERNEL_REPROJECT)
+KERNEL_REPROJECT = 10   # ptReprojectSampleBuffer and ptReprojectSampleBufferMoving (PT_KERNEL_REPROJECT)
 
 _vp = C.c_void_p
 _u32 = C.c_uint32
@@ -301,6 +306,9 @@ SCENE_API = {
     "ptsDenoisePair": (_i32, [_u32, _u32, _fptr, _fptr, _vp, C.POINTER(pt_denoise_pair_parameters), _fptr]),
     "ptsReproject": (_i32, [_u32, _u32, _fptr, _vp, C.POINTER(pt_packed_camera), _u32, _u32, _vp,
                             C.POINTER(pt_packed_camera), C.POINTER(pt_reproject_parameters), _fptr]),
+    "ptsShapeMotion": (_i32, [_vp, _u32, _vp, _u32, _vp]),
+    "ptsReprojectMoving": (_i32, [_u32, _u32, _fptr, _vp, C.POINTER(pt_packed_camera), _u32, _u32, _vp,
+                                  C.POINTER(pt_packed_camera), _vp, _u32, C.POINTER(pt_reproject_parameters), _fptr]),
     "ptsCentralCameraRay": (_i32, [C.POINTER(pt_packed_camera), _u32, _u32, _u32, _u32, _fptr, _fptr]),
     "ptsFrameStatistics": (_i32, [_u32, _u32, _fptr, _fptr, C.POINTER(pt_frame_statistics)]),
     "ptsStatsBin": (_i32, [C.c_float]),
@@ -374,6 +382,9 @@ HIP_API = {
     "ptDenoiseSampleBufferPair": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(pt_denoise_pair_parameters), _vp]),
     "ptReprojectSampleBuffer": (_i32, [_vp, _vp, _vp, C.POINTER(pt_packed_camera), _vp, C.POINTER(pt_packed_camera),
                                        C.POINTER(pt_reproject_parameters), _vp]),
+    "ptReprojectSampleBufferMoving": (_i32, [_vp, _vp, _vp, C.POINTER(pt_packed_camera), _vp,
+                                             C.POINTER(pt_packed_camera), _vp, _u32,
+                                             C.POINTER(pt_reproject_parameters), _vp]),
     "ptComputeFrameStatistics": (_i32, [_vp, _vp, _vp, C.POINTER(pt_frame_statistics)]),
     "ptAccumulateSampleBuffer": (_i32, [_vp, _vp, _vp]),
     "ptSetFrameStatisticsVariant": (_i32, [_vp, _u32]),

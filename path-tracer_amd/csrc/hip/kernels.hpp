@@ -151,6 +151,13 @@ hipError_t pt_launch_reproject(const float4* prev, const float4* prev_guides, ui
                                const pt_packed_camera* prev_camera, const float4* guides, uint32_t w, uint32_t h,
                                const pt_packed_camera* camera, const pt_reproject_parameters* p, float4* out,
                                hipStream_t st);
+// The same with a motion table: motion, motion_count
+// records in device memory, is read per pixel through the guide's shape index.
+hipError_t pt_launch_reproject_moving(const float4* prev, const float4* prev_guides, uint32_t wp, uint32_t hp,
+                                      const pt_packed_camera* prev_camera, const float4* guides, uint32_t w,
+                                      uint32_t h, const pt_packed_camera* camera, const pt_shape_motion* motion,
+                                      uint32_t motion_count, const pt_reproject_parameters* p, float4* out,
+                                      hipStream_t st);
 // dst += src per component.
 hipError_t pt_launch_accumulate(float4* dst, const float4* src, uint64_t n, hipStream_t st);
 // compact: the completion-queue instantiation (ShadeTile), for scenes whose

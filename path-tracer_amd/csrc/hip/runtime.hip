@@ -110,6 +110,14 @@ struct pt_device {
     // call, cleared on `stream` before every launch.
     pt_frame_statistics* stats = nullptr;
     uint32_t stats_variant = PT_STATS_VARIANT_AUTO;
+    // ptReprojectSampleBufferMoving's motion table on the device: grown on
+    // demand, rewritten on `stream` before every launch that reads it, from a
+    // pinned copy of the caller's table (so the caller's memory is done with
+    // when the call returns); motion_copied: that upload has left the copy.
+    dbuf<pt_shape_motion> motion;
+    pt_shape_motion* motion_host = nullptr;
+    size_t motion_host_count = 0;
+    hipEvent_t motion_copied = nullptr;
 };
 
 struct pt_scene {
@@ -543,6 +551,9 @@ void ptDestroyDevice(pt_device* d)
     }
     if (d->fork_event) (void)hipEventDestroy(d->fork_event);
     if (d->stats) (void)hipFree(d->stats);
+    d->motion.release();
+    if (d->motion_host) (void)hipHostFree(d->motion_host);
+    if (d->motion_copied) (void)hipEventDestroy(d->motion_copied);
     (void)hipStreamDestroy(d->stream);
     delete d;
 }
@@ -2285,6 +2296,62 @@ int ptReprojectSampleBuffer(pt_device* d, pt_sample_buffer* prev, pt_denoise_gui
     if (int e = BeginTimed(d, PT_KERNEL_REPROJECT, ep)) return e;
     PT_HIP(pt_launch_reproject(prev->accum, pg->records.ptr, pg->width, pg->height, pc, g->records.ptr, g->width,
                                g->height, c, p, dst->accum, d->stream));
+    if (int e = EndTimed(d, ep)) return e;
+    return 0;
+}
+
+// Row 9: the same checks, then the motion table's stream-ordered copy into the
+// device's own buffer and the moving-shape kernel.  Without a table (NULL, 0)
+// it is ptReprojectSampleBuffer.
+int ptReprojectSampleBufferMoving(pt_device* d, pt_sample_buffer* prev, pt_denoise_guides* pg,
+                                  const pt_packed_camera* pc, pt_denoise_guides* g, const pt_packed_camera* c,
+                                  const pt_shape_motion* motion, uint32_t motion_count,
+                                  const pt_reproject_parameters* p, pt_sample_buffer* dst)
+{
+    if (!motion && motion_count) { SetError("reproject: %u motion records at a null pointer", motion_count); return -1; }
+    if (!motion) return ptReprojectSampleBuffer(d, prev, pg, pc, g, c, p, dst);
+    if (!d || !prev || !pg || !pc || !g || !c || !p || !dst) { SetError("null argument"); return -1; }
+    if (prev == dst) { SetError("reproject: prev and dst are the same sample buffer"); return -1; }
+    if (pg == g) { SetError("reproject: prev_guides and guides are the same object"); return -1; }
+    if (prev->dev != d || dst->dev != d || pg->dev != d || g->dev != d) {
+        SetError("reproject: objects of another device");
+        return -1;
+    }
+    if (prev->width != pg->width || prev->height != pg->height || dst->width != g->width || dst->height != g->height) {
+        SetError("reproject: size mismatch (prev %ux%u, prev_guides %ux%u, guides %ux%u, dst %ux%u)", prev->width,
+                 prev->height, pg->width, pg->height, g->width, g->height, dst->width, dst->height);
+        return -1;
+    }
+    if (!pt_reproject_parameters_ok(p)) {
+        SetError("reproject: bad parameters (NormalCosine in (-1, 1], DepthTolerance > 0, MinWeight in (0, 1], "
+                 "MaxHistory > 0)");
+        return -1;
+    }
+    PT_HIP(hipSetDevice(d->id));
+    // Growing frees the old table; hipFree waits for the launches that read it.
+    PT_HIP(d->motion.alloc(motion_count));
+    if (motion_count) {
+        // The last call's upload may still be queued: it must have read the
+        // pinned copy before this call overwrites it.
+        if (!d->motion_copied) PT_HIP(hipEventCreateWithFlags(&d->motion_copied, hipEventDisableTiming));
+        PT_HIP(hipEventSynchronize(d->motion_copied));
+        if (motion_count > d->motion_host_count) {
+            if (d->motion_host) (void)hipHostFree(d->motion_host);
+            d->motion_host = nullptr;
+            d->motion_host_count = 0;
+            PT_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->motion_host), (size_t)motion_count * sizeof(pt_shape_motion),
+                                 hipHostMallocDefault));
+            d->motion_host_count = motion_count;
+        }
+        std::memcpy(d->motion_host, motion, (size_t)motion_count * sizeof(pt_shape_motion));
+        PT_HIP(hipMemcpyAsync(d->motion.ptr, d->motion_host, (size_t)motion_count * sizeof(pt_shape_motion),
+                              hipMemcpyHostToDevice, d->stream));
+        PT_HIP(hipEventRecord(d->motion_copied, d->stream));
+    }
+    event_pair ep{};
+    if (int e = BeginTimed(d, PT_KERNEL_REPROJECT, ep)) return e;
+    PT_HIP(pt_launch_reproject_moving(prev->accum, pg->records.ptr, pg->width, pg->height, pc, g->records.ptr, g->width,
+                                      g->height, c, d->motion.ptr, motion_count, p, dst->accum, d->stream));
     if (int e = EndTimed(d, ep)) return e;
     return 0;
 }

@@ -101,6 +101,7 @@ class DeviceScene:
         L = N.hip_lib()
         self.device = device
         self.cameras = np.zeros(0, dtype=N.CAMERA_DTYPE)
+        self.shapes = np.zeros(0, dtype=N.SHAPE_DTYPE)
         self._h = L.ptCreateScene(device.handle)
         if not self._h:
             raise PathTracerError(L.ptGetLastError().decode())
@@ -125,6 +126,11 @@ class DeviceScene:
         if packs.camera_count and packs.cameras:
             buf = (C.c_char * (packs.camera_count * N.CAMERA_DTYPE.itemsize)).from_address(packs.cameras)
             self.cameras = np.frombuffer(buf, dtype=N.CAMERA_DTYPE).copy()
+        # And the packed shapes (FrameHistory(follow_shapes=True) compares two frames' transforms).
+        self.shapes = np.zeros(0, dtype=N.SHAPE_DTYPE)
+        if packs.shape_count and packs.shapes:
+            buf = (C.c_char * (packs.shape_count * N.SHAPE_DTYPE.itemsize)).from_address(packs.shapes)
+            self.shapes = np.frombuffer(buf, dtype=N.SHAPE_DTYPE).copy()
 
     @property
     def stack_needed(self) -> int:
@@ -428,15 +434,45 @@ def _camera_struct(camera) -> N.pt_packed_camera:
     return N.pt_packed_camera.from_buffer_copy(c.tobytes())
 
 
+def shape_motion(prev_shapes: np.ndarray, shapes: np.ndarray) -> np.ndarray:
+    """The motion table between two packs of one scene (ptsShapeMotion,
+    pt_scene.h): prev_shapes and shapes are the packed
+    shape records (scene.arrays()["shapes"], DeviceScene.shapes) of the
+    previous and the current frame; returns one SHAPE_MOTION_DTYPE record per
+    current shape.  Shapes are matched by index: the set of entities must be
+    the same in both packs (only a longer array is noticed)."""
+    ps = np.ascontiguousarray(prev_shapes, dtype=N.SHAPE_DTYPE).reshape(-1)
+    cs = np.ascontiguousarray(shapes, dtype=N.SHAPE_DTYPE).reshape(-1)
+    out = np.zeros(cs.size, dtype=N.SHAPE_MOTION_DTYPE)
+    rc = N.scene_lib().ptsShapeMotion(ps.ctypes.data if ps.size else None, ps.size, cs.ctypes.data if cs.size else None,
+                                      cs.size, out.ctypes.data if cs.size else None)
+    if rc != 0:
+        raise PathTracerError(f"ptsShapeMotion: bad arguments (status {rc})")
+    return out
+
+
+def _motion_table(motion):
+    """(array kept alive, pointer or None, count) of an optional motion table."""
+    if motion is None:
+        return None, None, 0
+    m = np.ascontiguousarray(motion, dtype=N.SHAPE_MOTION_DTYPE).reshape(-1)
+    if m.size == 0:                      # an empty table is still a table: every hit is beyond it
+        m = np.zeros(1, dtype=N.SHAPE_MOTION_DTYPE)
+        return m, m.ctypes.data, 0
+    return m, m.ctypes.data, m.size
+
+
 def reproject_host(prev_accum: np.ndarray, prev_guides: np.ndarray, prev_camera, guides: np.ndarray, camera,
-                   params: "ReprojectParameters | None" = None) -> np.ndarray:
+                   params: "ReprojectParameters | None" = None, motion: "np.ndarray | None" = None) -> np.ndarray:
     """Temporal reprojection on the CPU (ptsReproject, libptscene.so), which
     the device kernel equals bit for bit.  prev_accum: (Hp, Wp, 4) accumulator
     of the previous view; prev_guides: its (Hp, Wp) DENOISE_GUIDE_DTYPE
     records; guides: the current view's (H, W) records; prev_camera, camera:
     the packed camera records (scene.arrays()["cameras"][i]) the two guide
     images were rendered with.  Returns (H, W, 4): (mean XYZ * n, n) with n
-    the carried sample count, zeros where the pixel has no history."""
+    the carried sample count, zeros where the pixel has no history.  motion:
+    a shape_motion() table; pixels of moved shapes then follow them
+    (ptsReprojectMoving)."""
     a = np.ascontiguousarray(prev_accum, dtype=np.float32)
     if a.ndim != 3 or a.shape[2] != 4:
         raise ValueError(f"accumulator of shape {a.shape}, expected (H, W, 4)")
@@ -449,6 +485,14 @@ def reproject_host(prev_accum: np.ndarray, prev_guides: np.ndarray, prev_camera,
     out = np.zeros(g.shape + (4,), np.float32)
     pc, c = _camera_struct(prev_camera), _camera_struct(camera)
     p = (params or ReprojectParameters()).as_struct()
+    if motion is not None:
+        m, mp, mn = _motion_table(motion)
+        rc = N.scene_lib().ptsReprojectMoving(a.shape[1], a.shape[0], N.fptr(a), pg.ctypes.data, C.byref(pc),
+                                              g.shape[1], g.shape[0], g.ctypes.data, C.byref(c), mp, mn, C.byref(p),
+                                              N.fptr(out))
+        if rc != 0:
+            raise PathTracerError(f"ptsReprojectMoving: bad arguments (status {rc})")
+        return out
     rc = N.scene_lib().ptsReproject(a.shape[1], a.shape[0], N.fptr(a), pg.ctypes.data, C.byref(pc), g.shape[1],
                                     g.shape[0], g.ctypes.data, C.byref(c), C.byref(p), N.fptr(out))
     if rc != 0:
@@ -568,21 +612,32 @@ class SampleBuffer:
         return dst
 
     def reproject(self, prev_guides: "DenoiseGuides", prev_camera, guides: "DenoiseGuides", camera,
-                  params: "ReprojectParameters | None" = None, out: "SampleBuffer | None" = None) -> "SampleBuffer":
+                  params: "ReprojectParameters | None" = None, out: "SampleBuffer | None" = None,
+                  motion: "np.ndarray | None" = None) -> "SampleBuffer":
         """Temporal reprojection on the device (ptReprojectSampleBuffer;
         enqueues): this buffer is the previous view's accumulator, prev_guides
         and prev_camera its guides and packed camera record, guides and camera
         the current view's.  `out` (a new sample buffer of the guides' size
         when None) receives (mean XYZ * n, n) per pixel, zeros where the pixel
         is disoccluded; a renderer with RENDER_FLAG_ACCUMULATE adds its
-        samples on top.  This buffer and both guides are not written."""
+        samples on top.  This buffer and both guides are not written.
+        motion: a shape_motion() table; pixels of moved shapes then follow
+        them (ptReprojectSampleBufferMoving)."""
         dst = out if out is not None else SampleBuffer(self.device, guides.width, guides.height)
         pc, c = _camera_struct(prev_camera), _camera_struct(camera)
         p = (params or ReprojectParameters()).as_struct()
         try:
-            _check(N.hip_lib().ptReprojectSampleBuffer(self.device.handle, self._h, prev_guides.handle, C.byref(pc),
-                                                       guides.handle, C.byref(c), C.byref(p), dst.handle),
-                   "ptReprojectSampleBuffer")
+            if motion is not None:
+                m, mp, mn = _motion_table(motion)
+                _check(N.hip_lib().ptReprojectSampleBufferMoving(self.device.handle, self._h, prev_guides.handle,
+                                                                 C.byref(pc), guides.handle, C.byref(c), mp, mn,
+                                                                 C.byref(p), dst.handle),
+                       "ptReprojectSampleBufferMoving")
+            else:
+                _check(N.hip_lib().ptReprojectSampleBuffer(self.device.handle, self._h, prev_guides.handle,
+                                                           C.byref(pc), guides.handle, C.byref(c), C.byref(p),
+                                                           dst.handle),
+                       "ptReprojectSampleBuffer")
         except PathTracerError:
             if out is None:
                 dst.close()
@@ -627,15 +682,23 @@ class SampleBuffer:
 
 
 class FrameHistory:
-    """Keeps the last frame (its sample buffer, guides and camera record) so
+    """Keeps the last frame (its sample buffer, guides, camera record and, with
+    follow_shapes, packed shapes) so
     that the next one starts from it: begin_frame() renders the new view's
     guides and reprojects the stored frame into the new sample buffer.  Thin
     glue over DenoiseGuides.render and SampleBuffer.reproject."""
 
-    def __init__(self, device: "Device", width: int, height: int, params: "ReprojectParameters | None" = None):
+    def __init__(self, device: "Device", width: int, height: int, params: "ReprojectParameters | None" = None,
+                 follow_shapes: bool = False):
+        """follow_shapes: also keep the frame's packed shapes and reproject
+        with the motion table between the two frames (shape_motion), so that
+        a moved object keeps its history.  The scene's entities must be the
+        same from frame to frame."""
         self.device = device
         self.width, self.height = int(width), int(height)
         self.params = params
+        self.follow_shapes = bool(follow_shapes)
+        self.shapes = None          # the last frame's packed shapes (follow_shapes)
         self._spare = DenoiseGuides(device, self.width, self.height)
         self.guides = None          # the current frame's guides (after begin_frame)
         self.buffer = None          # the sample buffer passed to the last begin_frame (non-owning)
@@ -657,8 +720,12 @@ class FrameHistory:
         guides = self._spare
         guides.render(ds, camera_index)
         carried = self.buffer is not None
+        shapes = ds.shapes.copy() if self.follow_shapes else None
         if carried:
-            self.buffer.reproject(self.guides, self.camera, guides, camera, self.params, out=sample_buffer)
+            motion = shape_motion(self.shapes, shapes) if self.follow_shapes else None
+            self.buffer.reproject(self.guides, self.camera, guides, camera, self.params, out=sample_buffer,
+                                  motion=motion)
+        self.shapes = shapes
         if self.guides is None:
             self._spare = DenoiseGuides(self.device, self.width, self.height)
         else:

@@ -27,11 +27,16 @@
   thread leaves before its tap loads), GB/s against the 96 B/pixel estimate, with
   ptRenderSampleBuffer and one a-trous iteration on the same buffers, at
   1920x1080 and 3840x2160; every figure three times.
+* reproject_moving (ptReprojectSampleBufferMoving, reproject.hip; DESIGN.md §6
+  row 9): the same pan with a motion table in which no shape moved and with
+  one in which every shape is flagged as moved (identity matrices, so the
+  same taps), beside ptReprojectSampleBuffer's kernel, ptRenderSampleBuffer
+  and one a-trous iteration in the same run; every figure three times.
 * host builds (§8(f) row 3): mesh BVH build of a 1.96 M-face mesh on 1 and
   on all of the job's threads, and the RGB -> spectrum table.
 
 Kernel times are HIP events on the device stream (ptGetKernelStats).
-Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|reproject|preview|openpbr|host ...]
+Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|reproject|reproject_moving|preview|openpbr|host ...]
 (default: all).
 """
 import json
@@ -268,6 +273,66 @@ def reproject(pt, dev):
     return out
 
 
+def reproject_moving(pt, dev):
+    """Per size, row8_ms: ptReprojectSampleBuffer after the small pan of
+    reproject(); static_ms, moved_ms: ptReprojectSampleBufferMoving on the
+    same inputs with a table of unmoved shapes and with every record flagged
+    MOVED (identity matrices: the same taps through the moved path; the
+    table's upload is not in the kernel's time); resolve_ms and
+    denoise_step1_ms: the yardsticks; shapes: the table's length; *_carried:
+    the share of pixels with a history.  Each time is a list: the mean of 10
+    timed calls after a warm-up call, taken three times in turn."""
+    out = {}
+    scene = pt.Scene.config(3)
+    cam = scene.find_camera(0)
+    ds = pt.DeviceScene(dev)
+    (px, py, pz), (rx, ry, rz) = C3_POSE
+    for W, H in ((1920, 1080), (3840, 2160)):
+        scene.move_camera(cam, position=(px, py, pz), rotation=(rx, ry, rz))
+        scene.pack()
+        ds.update(scene)
+        prev_cam = ds.cameras[0].copy()
+        prev, dst = pt.SampleBuffer(dev, W, H), pt.SampleBuffer(dev, W, H)
+        r = pt.BasicRenderer(dev, ds, prev)
+        r.RenderFlags = 3
+        r.reset()
+        r.run(8)
+        prev_guides, guides = pt.DenoiseGuides(dev, W, H), pt.DenoiseGuides(dev, W, H)
+        prev_guides.render(ds, 0)
+        scene.move_camera(cam, position=(px + 0.02, py + 0.02, pz), rotation=(rx, ry, rz + 0.02))
+        scene.pack()
+        ds.update(scene)
+        now_cam = ds.cameras[0].copy()
+        guides.render(ds, 0)
+        static = pt.shape_motion(ds.shapes, ds.shapes)
+        moved = static.copy()
+        moved["Flags"] = pt.SHAPE_MOTION_MOVED
+        runs = {"resolve_ms": (K_RESOLVE, lambda: prev.render(ToneMappingMode=pt.TONE_MAPPING_ACES)),
+                "denoise_step1_ms": (K_DENOISE, lambda: prev.denoise(prev_guides, pt.DenoiseParameters(Iterations=1),
+                                                                     out=dst)),
+                "row8_ms": (K_REPROJECT, lambda: prev.reproject(prev_guides, prev_cam, guides, now_cam, out=dst))}
+        for name, table in (("static", static), ("moved", moved)):
+            runs[f"{name}_ms"] = (K_REPROJECT, lambda table=table: prev.reproject(prev_guides, prev_cam, guides, now_cam,
+                                                                                   out=dst, motion=table))
+        res = {"pixels": W * H, "shapes": len(static)}
+        for key in runs:
+            res[key] = []
+        for _ in range(3):
+            for key, (kernel, fn) in runs.items():
+                fn()   # warm
+                ms, _ = timed(dev, kernel, fn, 10)
+                res[key].append(round(ms, 4))
+        for name, table in (("row8", None), ("static", static), ("moved", moved)):
+            prev.reproject(prev_guides, prev_cam, guides, now_cam, out=dst, motion=table)
+            res[f"{name}_carried"] = round(dst.statistics().filled / (W * H), 4)
+        out[f"{W}x{H}"] = res
+        for x in (guides, prev_guides, r, dst, prev):
+            x.close()
+    ds.close()
+    scene.close()
+    return out
+
+
 def preview(pt, dev):
     out = {}
     modes = {"base_color": pt.PREVIEW_RENDER_MODE_BASE_COLOR, "shaded": pt.PREVIEW_RENDER_MODE_BASE_COLOR_SHADED,
@@ -347,7 +412,8 @@ def host_builds(pt):
 
 def main():
     pt = load()
-    entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "reproject": reproject, "preview": preview, "openpbr": openpbr}
+    entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "reproject": reproject, "reproject_moving": reproject_moving,
+               "preview": preview, "openpbr": openpbr}
     want = sys.argv[1:] or list(entries) + ["host"]
     dev = pt.Device(0)
     res = {name: fn(pt, dev) for name, fn in entries.items() if name in want}

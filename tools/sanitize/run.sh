@@ -39,6 +39,7 @@ run asan_render "$A" render
 run asan_denoise "$A" denoise
 run asan_stats "$A" stats
 run asan_reproject "$A" reproject
+run asan_reproject_moving "$A" reproject_moving
 PT_BVH_THREADS=8 run tsan_bvh "$T" bvh 300000
 run tsan_render "$T" render
 PT_BVH_THREADS=8 run asan_bvh "$A" bvh 200000

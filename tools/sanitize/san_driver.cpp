@@ -21,6 +21,8 @@
 //                               small random, empty and NaN / inf / denormal
 //                               images, single and pair, one pixel included;
 //                               rejected arguments
+//   san_driver reproject_moving ptsShapeMotion and ptsReprojectMoving on random
+//                               tables with NaN and flagged records, 1x1 to 67x45
 //   san_driver reproject        ptsReproject and ptsCentralCameraRay on random
 //                               small frames (1x1 and differing previous and
 //                               current sizes included) under cameras of every
@@ -390,9 +392,118 @@ static int Reproject()
     return bad != 0;
 }
 
+// ptsShapeMotion and ptsReprojectMoving on random tables:
+// every flag combination, NaN / infinite / zero matrices, tables shorter than
+// the guides' shape indices, frames from 1x1 to 67x45.
+static int ReprojectMoving()
+{
+    std::mt19937 rng(14);
+    std::uniform_real_distribution<float> u(0.0f, 4.0f), s(-1.0f, 1.0f);
+    const float nan = std::nanf(""), inf = HUGE_VALF;
+    const float odd[] = {0.0f, -0.0f, -1.0f, nan, inf, -inf, 1e-45f, 1e-38f, 3e38f, 1.0f};
+    const size_t nodd = sizeof(odd) / sizeof(odd[0]);
+    const uint32_t sizes[][4] = {{1, 1, 1, 1}, {1, 1, 5, 3}, {7, 1, 1, 9}, {16, 16, 17, 16}, {29, 33, 37, 21},
+                                 {64, 40, 50, 37}, {67, 45, 67, 45}};
+    const float origin[3] = {0.0f, -4.0f, 1.0f}, aside[3] = {0.4f, -4.0f, 1.0f};
+    int bad = 0;
+    for (auto& z : sizes) {
+        const uint32_t Wp = z[0], Hp = z[1], W = z[2], H = z[3];
+        const size_t np = (size_t)Wp * Hp, n = (size_t)W * H;
+        for (uint32_t model = 0; model < 3; model++) {
+            const pt_packed_camera prev = SanCamera(model, aside, 0.1f), cur = SanCamera(model, origin, 0.0f);
+            for (uint32_t shapes = 0; shapes < 6; shapes += 1 + shapes / 2) {     // 0, 1, 2, 4 records; guides index 0..4 and beyond
+                // two packs: a small move, an equal transform, another type, a NaN, an odd value per shape
+                std::vector<pt_packed_shape> a(5), b(5);
+                for (int i = 0; i < 5; i++) {
+                    const float pos[3] = {s(rng), s(rng), u(rng)};
+                    const pt_packed_camera t0 = SanCamera(0, pos, s(rng)), t1 = SanCamera(0, aside, s(rng));
+                    a[i].Transform = t0.Transform;
+                    b[i].Transform = rng() % 3 == 0 ? t0.Transform : t1.Transform;
+                    a[i].Type = b[i].Type = 2;
+                    if (rng() % 5 == 0) b[i].Type = 3;
+                    if (rng() % 5 == 0) b[i].MeshRootNodeIndex = 7;
+                    if (rng() % 4 == 0) b[i].Transform.From[rng() % 16] = odd[rng() % nodd];
+                    if (rng() % 4 == 0) a[i].Transform.To[rng() % 16] = odd[rng() % nodd];
+                }
+                std::vector<pt_shape_motion> table(shapes + 1);
+                if (ptsShapeMotion(a.data(), shapes > 2 ? shapes - 1 : shapes, b.data(), shapes, table.data()) != 0) {
+                    std::printf("shape motion: failed\n");
+                    return 1;
+                }
+                for (uint32_t i = 0; i < shapes; i++) {
+                    bad += table[i].Flags > 2;
+                    if (table[i].Flags == PT_SHAPE_MOTION_NO_HISTORY)
+                        for (float v : table[i].Point) bad += v != 0.0f;
+                }
+                for (int kind = 0; kind < 3; kind++) {        // the table: as computed, flags scrambled, odd entries
+                    std::vector<pt_shape_motion> m(table.begin(), table.begin() + shapes);
+                    for (pt_shape_motion& r : m) {
+                        if (kind >= 1) r.Flags = rng() % 8;
+                        if (kind == 2)
+                            for (int k = 0; k < 4; k++) (rng() % 2 ? r.Point[rng() % 12] : r.Normal[rng() % 9]) = odd[rng() % nodd];
+                    }
+                    std::vector<float> acc(4 * np), out(4 * n, -1.0f);
+                    std::vector<pt_denoise_guide> gp(np), gc(n);
+                    for (size_t i = 0; i < 4 * np; i++)
+                        acc[i] = kind == 2 && rng() % 8 == 0 ? odd[rng() % nodd] : (i % 4 == 3 ? (float)(rng() % 5) : u(rng));
+                    for (std::vector<pt_denoise_guide>* g : {&gp, &gc}) {
+                        for (pt_denoise_guide& r : *g) {
+                            for (int k = 0; k < 3; k++) { r.normal[k] = s(rng); r.albedo[k] = 0.5f * u(rng); }
+                            r.time = rng() % 16 == 0 ? odd[rng() % nodd] : 1.0f + u(rng);
+                            r.shape = rng() % 4 == 0 ? 0xFFFFFFFFu : (rng() % 16 == 0 ? rng() : rng() % 5);
+                        }
+                    }
+                    pt_reproject_parameters p{0.5f, 0.5f, 0.25f, 8.0f};
+                    // shapes == 0: a table of no records (a valid pointer, count 0)
+                    if (ptsReprojectMoving(Wp, Hp, acc.data(), gp.data(), &prev, W, H, gc.data(), &cur, table.data(), 0, &p, out.data()) != 0 ||
+                        ptsReprojectMoving(Wp, Hp, acc.data(), gp.data(), &prev, W, H, gc.data(), &cur,
+                                           shapes ? m.data() : table.data(), shapes, &p, out.data()) != 0) {
+                        std::printf("reproject_moving: failed\n");
+                        return 1;
+                    }
+                    size_t carried = 0;
+                    for (size_t i = 0; i < n; i++) {
+                        carried += out[4 * i + 3] > 0.0f;
+                        bad += !(out[4 * i + 3] >= 0.0f);                       // a count, never NaN or negative
+                        bad += out[4 * i + 3] > 8.0f;                           // capped
+                        // beyond the table or flagged NO_HISTORY: nothing carried
+                        const uint32_t sh = gc[i].shape;
+                        if (sh != 0xFFFFFFFFu && (sh >= shapes || (m[sh].Flags & PT_SHAPE_MOTION_NO_HISTORY)))
+                            bad += out[4 * i + 3] != 0.0f;
+                    }
+                    std::printf("reproject_moving %ux%u -> %ux%u model %u records %u table %d: %zu of %zu pixels\n", Wp,
+                                Hp, W, H, model, shapes, kind, carried, n);
+                }
+            }
+        }
+    }
+    // rejected arguments leave `out` untouched; no table is ptsReproject
+    float acc[4] = {1, 1, 1, 1}, out[4] = {7, 7, 7, 7}, row8[4], none[4];
+    pt_denoise_guide gp{}, gc{};
+    pt_shape_motion m{};
+    const pt_packed_camera cam = SanCamera(0, origin, 0.0f);
+    pt_reproject_parameters ok{0.9f, 0.05f, 0.25f, 64.0f}, depth{0.9f, 0.0f, 0.25f, 64.0f};
+    bad += ptsReprojectMoving(1, 1, acc, &gp, &cam, 1, 1, &gc, &cam, nullptr, 1, &ok, out) == 0;
+    bad += ptsReprojectMoving(1, 1, nullptr, &gp, &cam, 1, 1, &gc, &cam, &m, 1, &ok, out) == 0;
+    bad += ptsReprojectMoving(1, 1, acc, &gp, &cam, 1, 1, &gp, &cam, &m, 1, &ok, out) == 0;
+    bad += ptsReprojectMoving(1, 1, acc, &gp, &cam, 0, 1, &gc, &cam, &m, 1, &ok, out) == 0;
+    bad += ptsReprojectMoving(1, 1, acc, &gp, &cam, 1, 1, &gc, &cam, &m, 1, &depth, out) == 0;
+    bad += ptsReprojectMoving(1, 1, acc, &gp, &cam, 1, 1, &gc, &cam, &m, 1, &ok, nullptr) == 0;
+    bad += ptsReprojectMoving(1, 1, acc, &gp, &cam, 1, 1, &gc, nullptr, nullptr, 0, &ok, out) == 0;
+    for (float v : out) bad += v != 7.0f;
+    bad += ptsShapeMotion(nullptr, 1, nullptr, 0, nullptr) == 0;
+    bad += ptsShapeMotion(nullptr, 0, nullptr, 1, &m) == 0;
+    bad += ptsShapeMotion(nullptr, 0, nullptr, 0, nullptr) != 0;
+    bad += ptsReproject(1, 1, acc, &gp, &cam, 1, 1, &gc, &cam, &ok, row8) != 0;
+    bad += ptsReprojectMoving(1, 1, acc, &gp, &cam, 1, 1, &gc, &cam, nullptr, 0, &ok, none) != 0;
+    bad += std::memcmp(row8, none, sizeof(row8)) != 0;
+    std::printf("reproject_moving: %d checks wrong\n", bad);
+    return bad != 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise|stats|reproject ...\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise|stats|reproject|reproject_moving ...\n"); return 2; }
     std::string cmd = argv[1];
     if (cmd == "decode") return Decode(argc - 2, argv + 2);
     if (cmd == "model") return Model(argc - 2, argv + 2);
@@ -402,6 +513,7 @@ int main(int argc, char** argv)
     if (cmd == "denoise") return Denoise();
     if (cmd == "stats") return Stats();
     if (cmd == "reproject") return Reproject();
+    if (cmd == "reproject_moving") return ReprojectMoving();
     std::fprintf(stderr, "unknown command %s\n", cmd.c_str());
     return 2;
 }
