@@ -7,6 +7,9 @@
  * contraction, sums left to right, pt_sin / pt_cos / pt_atan2 / pt_asin /
  * pt_sqrt.  Per-pixel and per-tap arithmetic only: the loop over the image,
  * the loads of the four taps and the store of the result are the callers'.
+ * What rows 8 and 9 have in common is written once: the central ray, the
+ * position in the previous frame (pt_reproject_locate_tail) and the history
+ * and depth tests of a tap; row 9 adds only what a motion record changes.
  *
  * For a pixel of the current view: its central camera ray, the world point
  * its guide record saw (or the ray's direction on a miss), that point's
@@ -70,9 +73,10 @@ PT_HD int pt_reproject_camera_ok(const pt_packed_camera* Cam)
 
 /* The central camera ray of pixel (x, y) of a w x h frame: GenerateCameraRay
  * (src/scene/scene.glsl.inc:613-655) at the pixel centre through the lens
- * centre, then the packed velocity's round trip.  The guide kernel's
- * CentralCameraRay (csrc/hip/denoise.hip) restated.  0: unknown model, O = 0,
- * V = (0, 0, 1). */
+ * centre, then the packed velocity's round trip.  The guide kernel
+ * (csrc/hip/denoise.hip) takes its rays from here too, so the ray a guide
+ * record was seen along is the ray reprojection inverts.  0: unknown model,
+ * O = 0, V = (0, 0, 1). */
 PT_HD int pt_reproject_central_ray(const pt_packed_camera* Cam, uint32_t x, uint32_t y, uint32_t w, uint32_t h,
                                    pt3* RO, pt3* RV)
 {
@@ -132,10 +136,28 @@ typedef struct pt_reproject_target {
     float   dist;       /* hits: the world point's distance from the previous camera */
 } pt_reproject_target;
 
+/* Step 3, shared by rows 8 and 9: L, the point (or direction) in the previous
+ * camera's frame, to its continuous position in the wp x hp previous frame
+ * and that position's first tap and fractions.  0: behind the previous
+ * camera, or a position none of whose taps can lie inside the frame, a
+ * non-finite one included. */
+PT_HD int pt_reproject_locate_tail(const pt_packed_camera* Cp, pt3 L, uint32_t wp, uint32_t hp,
+                                   pt_reproject_target* T)
+{
+    float Nx, Ny;
+    if (!pt_reproject_project(Cp, L, &Nx, &Ny)) return 0;
+    float u = Nx * (float)wp - 0.5f, v = Ny * (float)hp - 0.5f;
+    if (!(u > -1.0f && u < (float)wp && v > -1.0f && v < (float)hp)) return 0;
+    float fu = pt_floor(u), fv = pt_floor(v);
+    T->x0 = (int64_t)fu;
+    T->y0 = (int64_t)fv;
+    T->fx = u - fu;
+    T->fy = v - fv;
+    return 1;
+}
+
 /* Steps 1-3.  shape, time: the current pixel's guide record.  0: no history
- * (a camera this header cannot invert, a point behind the previous camera, or
- * a position none of whose taps can lie inside the wp x hp previous frame,
- * a non-finite one included). */
+ * (a camera this header cannot invert, or pt_reproject_locate_tail's 0). */
 PT_HD int pt_reproject_locate(const pt_packed_camera* Cc, const pt_packed_camera* Cp, uint32_t x, uint32_t y,
                               uint32_t w, uint32_t h, uint32_t wp, uint32_t hp, uint32_t shape, float time,
                               pt_reproject_target* T)
@@ -152,16 +174,7 @@ PT_HD int pt_reproject_locate(const pt_packed_camera* Cc, const pt_packed_camera
     } else {
         L = mat4_mul_vector(Cp->Transform.From, V);
     }
-    float Nx, Ny;
-    if (!pt_reproject_project(Cp, L, &Nx, &Ny)) return 0;
-    float u = Nx * (float)wp - 0.5f, v = Ny * (float)hp - 0.5f;
-    if (!(u > -1.0f && u < (float)wp && v > -1.0f && v < (float)hp)) return 0;
-    float fu = pt_floor(u), fv = pt_floor(v);
-    T->x0 = (int64_t)fu;
-    T->y0 = (int64_t)fv;
-    T->fx = u - fu;
-    T->fy = v - fv;
-    return 1;
+    return pt_reproject_locate_tail(Cp, L, wp, hp, T);
 }
 
 /* Bilinear weight of tap i = 0..3 ((0,0), (1,0), (0,1), (1,1)). */
@@ -172,19 +185,32 @@ PT_HD float pt_reproject_tap_weight(const pt_reproject_target* T, int i)
     return wx * wy;
 }
 
+/* Step 4's two tests that rows 8 and 9 share.  A tap's accumulator value hp
+ * is a usable history: finite sums and a positive, finite sample count. */
+PT_HD int pt_reproject_history_ok(const float* hp)
+{
+    return pt_reproject_finite(hp[0]) && pt_reproject_finite(hp[1]) && pt_reproject_finite(hp[2]) &&
+           pt_reproject_finite(hp[3]) && hp[3] > 0.0f;
+}
+
+/* The tap's guide saw its surface at the distance the target expects. */
+PT_HD int pt_reproject_depth_ok(const pt_reproject_parameters* p, const pt_reproject_target* T,
+                                const pt_denoise_guide* gp)
+{
+    return pt_abs(gp->time - T->dist) <= p->DepthTolerance * T->dist;
+}
+
 /* Step 4 for a tap inside the previous image: hp its accumulator value, gp
  * its guide record, gc the current pixel's. */
 PT_HD int pt_reproject_tap_valid(const pt_reproject_parameters* p, const pt_reproject_target* T,
                                  const pt_denoise_guide* gc, const float* hp, const pt_denoise_guide* gp)
 {
-    if (!(pt_reproject_finite(hp[0]) && pt_reproject_finite(hp[1]) && pt_reproject_finite(hp[2]) &&
-          pt_reproject_finite(hp[3]) && hp[3] > 0.0f))
-        return 0;
+    if (!pt_reproject_history_ok(hp)) return 0;
     if (gp->shape != gc->shape) return 0;
     if (gc->shape == PT_SHAPE_INDEX_NONE) return 1;
     float d = (gp->normal[0] * gc->normal[0] + gp->normal[1] * gc->normal[1]) + gp->normal[2] * gc->normal[2];
     if (!(d >= p->NormalCosine)) return 0;
-    return pt_abs(gp->time - T->dist) <= p->DepthTolerance * T->dist;
+    return pt_reproject_depth_ok(p, T, gp);
 }
 
 /* Step 5: the sums over the valid taps, in tap order. */
@@ -258,16 +284,7 @@ PT_HD int pt_reproject_locate_moved(const pt_packed_camera* Cc, const pt_packed_
     float q = dot(N, N);
     if (!(q > 0.0f) || !pt_reproject_finite(q)) return 0;
     *Ne = N * (1.0f / pt_sqrt(q));
-    float Nx, Ny;
-    if (!pt_reproject_project(Cp, L, &Nx, &Ny)) return 0;
-    float u = Nx * (float)wp - 0.5f, v = Ny * (float)hp - 0.5f;
-    if (!(u > -1.0f && u < (float)wp && v > -1.0f && v < (float)hp)) return 0;
-    float fu = pt_floor(u), fv = pt_floor(v);
-    T->x0 = (int64_t)fu;
-    T->y0 = (int64_t)fv;
-    T->fx = u - fu;
-    T->fy = v - fv;
-    return 1;
+    return pt_reproject_locate_tail(Cp, L, wp, hp, T);
 }
 
 /* Step 4 for a tap of a moved shape's pixel: pt_reproject_tap_valid with the
@@ -275,13 +292,11 @@ PT_HD int pt_reproject_locate_moved(const pt_packed_camera* Cc, const pt_packed_
 PT_HD int pt_reproject_tap_valid_moved(const pt_reproject_parameters* p, const pt_reproject_target* T, uint32_t shape,
                                        pt3 Ne, const float* hp, const pt_denoise_guide* gp)
 {
-    if (!(pt_reproject_finite(hp[0]) && pt_reproject_finite(hp[1]) && pt_reproject_finite(hp[2]) &&
-          pt_reproject_finite(hp[3]) && hp[3] > 0.0f))
-        return 0;
+    if (!pt_reproject_history_ok(hp)) return 0;
     if (gp->shape != shape) return 0;
     float d = (gp->normal[0] * Ne.x + gp->normal[1] * Ne.y) + gp->normal[2] * Ne.z;
     if (!(d >= p->NormalCosine)) return 0;
-    return pt_abs(gp->time - T->dist) <= p->DepthTolerance * T->dist;
+    return pt_reproject_depth_ok(p, T, gp);
 }
 
 #endif /* PT_REPROJECT_H */

@@ -4,30 +4,32 @@
 // accumulator-shaped image.
 //
 // Guides: one primary ray per pixel, the central ray of GenerateCameraRay
-// (kernels.hip GenerateNewPath with jitter off and the lens point at the lens
-// centre), through the same Trace() as the extend kernel and the same hit
+// (include/pt_reproject.h's pt_reproject_central_ray, the one reprojection
+// inverts), through the same Trace() as the extend kernel and the same hit
 // attribute code as ptTraceRays' records; pixels map in 16x16 tiles like the
 // preview kernel.
 //
-// Filter: one launch per iteration between two float4 images (.w = 1: the
-// pixel has a colour, 0: empty).  The per-tap arithmetic is
-// include/pt_denoise.h's, shared with the host implementation
+// Filter: one launch per iteration between two float4 images.  The per-tap
+// arithmetic is include/pt_denoise.h's, shared with the host implementation
 // (csrc/scene/denoise.cpp); taps run dy outer, dx inner, sums left to right,
-// no atomics.  Two variants of the same function:
+// no atomics.  Two kernels, one per memory strategy, computing the same bits:
 //   gather   every tap read from global memory (25 x 48 B per pixel);
 //   lattice  a block owns a 16x16 set of pixels of ONE residue class of the
 //            step lattice (x = rx, y = ry mod step), so its taps fall in a
 //            20x20 lattice window whatever the step is; the window is staged
 //            in LDS once (400 x 48 B) and the 25 taps read LDS.
-//
-// Pair filter: the same two variants over a working
-// image {colour, luminance variance}, behind one prepare launch that forms
-// the combined frame of two half renders and its prefiltered variance.
+// Each is a template over a filter policy, which says what an image record
+// is and what a tap does with it: single_filter (row 5: colour, .w = 1, or 0
+// for an empty pixel) and pair_filter (a working image
+// {colour, luminance variance}, behind one prepare launch that forms the
+// combined frame of two half renders and its prefiltered variance).  The
+// policy is resolved at compile time; the loops exist once.
 #include "pt_device.hpp"
 #include "traverse.hpp"
 #include "kernels.hpp"
 #include "base_color.hpp"
 #include "../../../include/pt_denoise.h"
+#include "../../../include/pt_reproject.h"
 
 namespace ptd {
 
@@ -38,42 +40,6 @@ struct guide_args {
     uint32_t w, h;
     uint32_t tiles_x;
 };
-
-// GenerateCameraRay's central ray (kernels.hip:868-894 with SamplePosition =
-// pixel + 0.5 and the lens point O = 0: no random number), then the packed
-// velocity round trip every ray of the integrator takes between raygen and
-// extend (TileOrderStoreRay / ray_source_slots::load).  False: unknown model.
-PT_DEV bool CentralCameraRay(const dscene& S, const guide_args& P, uint32_t x, uint32_t y, pt3& RO, pt3& RV)
-{
-    float SPx = (float)x, SPy = (float)y;
-    SPx = SPx + 0.5f; SPy = SPy + 0.5f;
-    float Nx = SPx / (float)P.w, Ny = SPy / (float)P.h;
-    const pt_packed_camera* Cam = &S.cameras[P.camera];
-    uint32_t Model = Cam->Model;
-    pt3 O, V;
-    if (Model == PT_CAMERA_MODEL_PINHOLE || Model == PT_CAMERA_MODEL_THIN_LENS) {
-        pt3 SP = v3(-Cam->SensorSize[0] * (Nx - 0.5f), -Cam->SensorSize[1] * (0.5f - Ny), Cam->SensorDistance);
-        O = v3(0, 0, 0);
-        if (Model == PT_CAMERA_MODEL_PINHOLE) {
-            V = normalize(O - SP);
-        } else {
-            pt3 OP = -SP * Cam->FocalLength / (SP.z - Cam->FocalLength);
-            V = normalize(OP - O);
-        }
-    } else if (Model == PT_CAMERA_MODEL_360) {
-        float Phi = (Nx - 0.5f) * PT_TAU;
-        float Theta = (0.5f - Ny) * PT_PI;
-        O = v3(0, 0, 0);
-        V = v3(pt_cos(Theta) * pt_sin(Phi), pt_sin(Theta), -pt_cos(Theta) * pt_cos(Phi));
-    } else {
-        RO = v3s(0); RV = v3(0, 0, 1);
-        return false;
-    }
-    const float* To = Cam->Transform.To;
-    RO = mat4_mul_point(To, O);
-    RV = UnpackUnitVector(PackUnitVector(mat4_mul_vector(To, V)));
-    return true;
-}
 
 struct ray_source_guides {
     const dscene* S;
@@ -91,7 +57,9 @@ struct ray_source_guides {
         uint32_t x, y;
         pixel(i, x, y);
         D = PT_HIT_TIME_LIMIT;
-        return CentralCameraRay(*S, *P, x, y, O, V);
+        // The packed velocity's round trip every ray of the integrator takes
+        // between raygen and extend is part of it.  False: unknown model.
+        return pt_reproject_central_ray(&S->cameras[P->camera], x, y, P->w, P->h, &O, &V);
     }
 };
 
@@ -200,32 +168,6 @@ PT_DEV void Tap(tap_sums& A, const pt_denoise_pixel& p, float4 c, float4 ga, flo
     A.w = A.w + w;
 }
 
-template <bool FIRST>
-__global__ __launch_bounds__(256) void denoise_gather_kernel(const float4* __restrict__ in,
-                                                             const float4* __restrict__ guides, denoise_args P,
-                                                             float4* __restrict__ out)
-{
-    const uint32_t x = blockIdx.x * 16 + (threadIdx.x & 15u), y = blockIdx.y * 16 + (threadIdx.x >> 4);
-    if (x >= P.w || y >= P.h) return;
-    const size_t ip = (size_t)y * P.w + x;
-    float4 cp = LoadColor<FIRST>(in, ip);
-    if (!(cp.w > 0.0f)) { out[ip] = make_float4(0, 0, 0, 0); return; }
-    const pt_denoise_pixel p = MakePixel(cp, guides[2 * ip], guides[2 * ip + 1]);
-    tap_sums A{0.0f, 0.0f, 0.0f, 0.0f};
-    for (int dy = -2; dy <= 2; dy++) {
-        const int64_t qy = (int64_t)y + (int64_t)dy * (int64_t)P.step;
-        if (qy < 0 || qy >= (int64_t)P.h) continue;
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            const int64_t qx = (int64_t)x + (int64_t)dx * (int64_t)P.step;
-            if (qx < 0 || qx >= (int64_t)P.w) continue;
-            const size_t iq = (size_t)qy * P.w + (size_t)qx;
-            Tap(A, p, LoadColor<FIRST>(in, iq), guides[2 * iq], guides[2 * iq + 1], dx, dy, P.sg);
-        }
-    }
-    out[ip] = make_float4(A.x / A.w, A.y / A.w, A.z / A.w, 1.0f);
-}
-
 // LDS window: 20 rows of 20 records in three 16-B arrays (colour, {normal,
 // time}, {albedo, shape}), row stride 32 records = 512 B.  A wave reads 4
 // window rows x 16 consecutive records per tap with ds_read_b128, whose
@@ -270,45 +212,6 @@ struct lattice_block {
         return true;
     }
 };
-
-template <bool FIRST>
-__global__ __launch_bounds__(256) void denoise_lattice_kernel(const float4* __restrict__ in,
-                                                              const float4* __restrict__ guides, denoise_args P,
-                                                              float4* __restrict__ out)
-{
-    __shared__ float4 sc[DN_WIN * DN_ROW], sa[DN_WIN * DN_ROW], sb[DN_WIN * DN_ROW];
-    const lattice_block blk(P);
-    for (uint32_t r = threadIdx.x; r < DN_WIN * DN_WIN; r += 256) {
-        uint32_t slot;
-        size_t iq;
-        float4 c = make_float4(0, 0, 0, 0), ga = c, gb = c;
-        if (blk.record(P, r, slot, iq)) {
-            c = LoadColor<FIRST>(in, iq);
-            ga = guides[2 * iq];
-            gb = guides[2 * iq + 1];
-        }
-        sc[slot] = c;      // outside the image: .w = 0, skipped like an empty pixel
-        sa[slot] = ga;
-        sb[slot] = gb;
-    }
-    __syncthreads();
-    uint32_t ic;
-    size_t ip;
-    if (!blk.pixel(P, ic, ip)) return;
-    float4 cp = sc[ic];
-    if (!(cp.w > 0.0f)) { out[ip] = make_float4(0, 0, 0, 0); return; }
-    const pt_denoise_pixel p = MakePixel(cp, sa[ic], sb[ic]);
-    tap_sums A{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int dy = -2; dy <= 2; dy++) {
-#pragma unroll
-        for (int dx = -2; dx <= 2; dx++) {
-            const uint32_t iq = (uint32_t)((int)ic + dy * (int)DN_ROW + dx);
-            Tap(A, p, sc[iq], sa[iq], sb[iq], dx, dy, P.sg);
-        }
-    }
-    out[ip] = make_float4(A.x / A.w, A.y / A.w, A.z / A.w, 1.0f);
-}
 
 // Iterations = 0: the accumulator's mean, .w = 1 (0, 0, 0, 0 where empty).
 __global__ __launch_bounds__(256) void denoise_mean_kernel(const float4* __restrict__ accum, uint32_t n,
@@ -423,19 +326,69 @@ PT_DEV float4 PairResult(const pair_sums& A)
     return make_float4(A.x / A.w, A.y / A.w, A.z / A.w, LAST ? 1.0f : A.v / (A.w * A.w));
 }
 
+// --- the two filters as policies, and the two kernels over them --------------------
+//
+// A policy F gives: args (a filter_grid with the filter's sigmas), sums and
+// centre (the running sums, and what is set up once per centre pixel); load
+// (an image record as the taps see it); outside (the record stored for a
+// window slot outside the image, which the tap skips like an empty pixel);
+// empty / empty_result (the test on a centre record, and what an empty centre
+// writes); setup, tap and result.  Everything is static and inlined: a kernel
+// instantiation holds no trace of the other filter.
+
+// FIRST: iteration 0, which reads the accumulator.
+template <bool FIRST>
+struct single_filter {
+    using args = denoise_args;
+    using sums = tap_sums;
+    struct centre {};
+    static PT_DEV float4 load(const float4* __restrict__ in, size_t i) { return LoadColor<FIRST>(in, i); }
+    static PT_DEV float4 outside() { return make_float4(0, 0, 0, 0); }
+    static PT_DEV bool empty(float4 c) { return !(c.w > 0.0f); }
+    static PT_DEV float4 empty_result() { return make_float4(0, 0, 0, 0); }
+    static PT_DEV centre setup(const args&, float4) { return {}; }
+    static PT_DEV void tap(sums& A, const pt_denoise_pixel& p, centre, float4 c, float4 ga, float4 gb, int dx, int dy,
+                           const args& P)
+    {
+        Tap(A, p, c, ga, gb, dx, dy, P.sg);
+    }
+    static PT_DEV float4 result(const sums& A) { return make_float4(A.x / A.w, A.y / A.w, A.z / A.w, 1.0f); }
+};
+
+// LAST: the last iteration, which writes the sample-buffer form.  The
+// variance rides in the colour record's .w, so the lattice kernel's LDS
+// footprint is the single filter's.
 template <bool LAST>
-__global__ __launch_bounds__(256) void denoise_pair_gather_kernel(const float4* __restrict__ in,
-                                                                  const float4* __restrict__ guides, pair_args P,
-                                                                  float4* __restrict__ out)
+struct pair_filter {
+    using args = pair_args;
+    using sums = pair_sums;
+    using centre = float;       // D, the centre's luminance scale
+    static PT_DEV float4 load(const float4* __restrict__ in, size_t i) { return in[i]; }
+    static PT_DEV float4 outside() { return PairEmpty(false); }
+    static PT_DEV bool empty(float4 c) { return c.w < 0.0f; }
+    static PT_DEV float4 empty_result() { return PairEmpty(LAST); }
+    static PT_DEV centre setup(const args& P, float4 cp) { return pt_denoise_pair_scale(&P.sg, cp.w); }
+    static PT_DEV void tap(sums& A, const pt_denoise_pixel& p, centre D, float4 c, float4 ga, float4 gb, int dx, int dy,
+                           const args& P)
+    {
+        PairTap(A, p, D, c, ga, gb, dx, dy, P.sg);
+    }
+    static PT_DEV float4 result(const sums& A) { return PairResult<LAST>(A); }
+};
+
+template <class F>
+__global__ __launch_bounds__(256) void filter_gather_kernel(const float4* __restrict__ in,
+                                                            const float4* __restrict__ guides, typename F::args P,
+                                                            float4* __restrict__ out)
 {
     const uint32_t x = blockIdx.x * 16 + (threadIdx.x & 15u), y = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (x >= P.w || y >= P.h) return;
     const size_t ip = (size_t)y * P.w + x;
-    const float4 cp = in[ip];
-    if (cp.w < 0.0f) { out[ip] = PairEmpty(LAST); return; }
+    const float4 cp = F::load(in, ip);
+    if (F::empty(cp)) { out[ip] = F::empty_result(); return; }
     const pt_denoise_pixel p = MakePixel(cp, guides[2 * ip], guides[2 * ip + 1]);
-    const float D = pt_denoise_pair_scale(&P.sg, cp.w);
-    pair_sums A{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    const typename F::centre C = F::setup(P, cp);
+    typename F::sums A{};
     for (int dy = -2; dy <= 2; dy++) {
         const int64_t qy = (int64_t)y + (int64_t)dy * (int64_t)P.step;
         if (qy < 0 || qy >= (int64_t)P.h) continue;
@@ -444,31 +397,29 @@ __global__ __launch_bounds__(256) void denoise_pair_gather_kernel(const float4* 
             const int64_t qx = (int64_t)x + (int64_t)dx * (int64_t)P.step;
             if (qx < 0 || qx >= (int64_t)P.w) continue;
             const size_t iq = (size_t)qy * P.w + (size_t)qx;
-            PairTap(A, p, D, in[iq], guides[2 * iq], guides[2 * iq + 1], dx, dy, P.sg);
+            F::tap(A, p, C, F::load(in, iq), guides[2 * iq], guides[2 * iq + 1], dx, dy, P);
         }
     }
-    out[ip] = PairResult<LAST>(A);
+    out[ip] = F::result(A);
 }
 
-// The lattice kernel's window and arrays; the variance rides in the colour
-// record's .w, so the LDS footprint is the single-buffer kernel's.
-template <bool LAST>
-__global__ __launch_bounds__(256) void denoise_pair_lattice_kernel(const float4* __restrict__ in,
-                                                                   const float4* __restrict__ guides, pair_args P,
-                                                                   float4* __restrict__ out)
+template <class F>
+__global__ __launch_bounds__(256) void filter_lattice_kernel(const float4* __restrict__ in,
+                                                             const float4* __restrict__ guides, typename F::args P,
+                                                             float4* __restrict__ out)
 {
     __shared__ float4 sc[DN_WIN * DN_ROW], sa[DN_WIN * DN_ROW], sb[DN_WIN * DN_ROW];
     const lattice_block blk(P);
     for (uint32_t r = threadIdx.x; r < DN_WIN * DN_WIN; r += 256) {
         uint32_t slot;
         size_t iq;
-        float4 c = PairEmpty(false), ga = make_float4(0, 0, 0, 0), gb = ga;
+        float4 c = F::outside(), ga = make_float4(0, 0, 0, 0), gb = ga;
         if (blk.record(P, r, slot, iq)) {
-            c = in[iq];
+            c = F::load(in, iq);
             ga = guides[2 * iq];
             gb = guides[2 * iq + 1];
         }
-        sc[slot] = c;      // outside the image: .w = -1, skipped like an empty pixel
+        sc[slot] = c;
         sa[slot] = ga;
         sb[slot] = gb;
     }
@@ -477,19 +428,19 @@ __global__ __launch_bounds__(256) void denoise_pair_lattice_kernel(const float4*
     size_t ip;
     if (!blk.pixel(P, ic, ip)) return;
     const float4 cp = sc[ic];
-    if (cp.w < 0.0f) { out[ip] = PairEmpty(LAST); return; }
+    if (F::empty(cp)) { out[ip] = F::empty_result(); return; }
     const pt_denoise_pixel p = MakePixel(cp, sa[ic], sb[ic]);
-    const float D = pt_denoise_pair_scale(&P.sg, cp.w);
-    pair_sums A{0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    const typename F::centre C = F::setup(P, cp);
+    typename F::sums A{};
 #pragma unroll
     for (int dy = -2; dy <= 2; dy++) {
 #pragma unroll
         for (int dx = -2; dx <= 2; dx++) {
             const uint32_t iq = (uint32_t)((int)ic + dy * (int)DN_ROW + dx);
-            PairTap(A, p, D, sc[iq], sa[iq], sb[iq], dx, dy, P.sg);
+            F::tap(A, p, C, sc[iq], sa[iq], sb[iq], dx, dy, P);
         }
     }
-    out[ip] = PairResult<LAST>(A);
+    out[ip] = F::result(A);
 }
 
 }  // namespace ptd
@@ -526,22 +477,28 @@ static dim3 FilterGrid(ptd::filter_grid& P, uint32_t w, uint32_t h, uint32_t ite
     return dim3(P.ncx * ((lw + 15) / 16), P.ncy * ((lh + 15) / 16));
 }
 
+// One iteration of filter F<flag>: P holds the sigmas already; the geometry
+// and the kernel of the memory strategy are chosen here.
+template <template <bool> class F>
+static hipError_t LaunchFilter(const float4* in, const float4* guides, typename F<true>::args& P, uint32_t w,
+                               uint32_t h, uint32_t iteration, bool flag, bool lattice, float4* out, hipStream_t st)
+{
+    if (w == 0 || h == 0) return hipSuccess;
+    const dim3 grid = FilterGrid(P, w, h, iteration, lattice);
+    void (*kernel)(const float4*, const float4*, typename F<true>::args, float4*) =
+        lattice ? (flag ? ptd::filter_lattice_kernel<F<true>> : ptd::filter_lattice_kernel<F<false>>)
+                : (flag ? ptd::filter_gather_kernel<F<true>> : ptd::filter_gather_kernel<F<false>>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, st, in, guides, P, out);
+    return hipGetLastError();
+}
+
 hipError_t pt_launch_denoise(const float4* in, bool accumulator, const float4* guides, uint32_t w, uint32_t h,
                              const pt_denoise_parameters* p, uint32_t iteration, bool lattice, float4* out,
                              hipStream_t st)
 {
-    if (w == 0 || h == 0) return hipSuccess;
     ptd::denoise_args P;
-    const dim3 grid = FilterGrid(P, w, h, iteration, lattice);
     P.sg = pt_denoise_iteration_sigmas(p, iteration);
-    if (lattice) {
-        if (accumulator) hipLaunchKernelGGL(ptd::denoise_lattice_kernel<true>, grid, dim3(256), 0, st, in, guides, P, out);
-        else hipLaunchKernelGGL(ptd::denoise_lattice_kernel<false>, grid, dim3(256), 0, st, in, guides, P, out);
-    } else {
-        if (accumulator) hipLaunchKernelGGL(ptd::denoise_gather_kernel<true>, grid, dim3(256), 0, st, in, guides, P, out);
-        else hipLaunchKernelGGL(ptd::denoise_gather_kernel<false>, grid, dim3(256), 0, st, in, guides, P, out);
-    }
-    return hipGetLastError();
+    return LaunchFilter<ptd::single_filter>(in, guides, P, w, h, iteration, accumulator, lattice, out, st);
 }
 
 hipError_t pt_launch_denoise_mean(const float4* accum, uint32_t n, float4* out, hipStream_t st)
@@ -565,16 +522,7 @@ hipError_t pt_launch_denoise_pair(const float4* in, const float4* guides, uint32
                                   const pt_denoise_pair_parameters* p, uint32_t iteration, bool last, bool lattice,
                                   float4* out, hipStream_t st)
 {
-    if (w == 0 || h == 0) return hipSuccess;
     ptd::pair_args P;
-    const dim3 grid = FilterGrid(P, w, h, iteration, lattice);
     P.sg = pt_denoise_pair_make_sigmas(p);
-    if (lattice) {
-        if (last) hipLaunchKernelGGL(ptd::denoise_pair_lattice_kernel<true>, grid, dim3(256), 0, st, in, guides, P, out);
-        else hipLaunchKernelGGL(ptd::denoise_pair_lattice_kernel<false>, grid, dim3(256), 0, st, in, guides, P, out);
-    } else {
-        if (last) hipLaunchKernelGGL(ptd::denoise_pair_gather_kernel<true>, grid, dim3(256), 0, st, in, guides, P, out);
-        else hipLaunchKernelGGL(ptd::denoise_pair_gather_kernel<false>, grid, dim3(256), 0, st, in, guides, P, out);
-    }
-    return hipGetLastError();
+    return LaunchFilter<ptd::pair_filter>(in, guides, P, w, h, iteration, last, lattice, out, st);
 }

@@ -144,20 +144,16 @@ hipError_t pt_launch_denoise_pair(const float4* in, const float4* guides, uint32
 uint32_t pt_frame_statistics_grid(uint64_t n, uint32_t cu_count);
 hipError_t pt_launch_frame_statistics(const float4* a, const float4* b, uint64_t n, uint32_t cu_count, bool uniform,
                                       pt_frame_statistics* out, hipStream_t st);
-// Temporal reprojection (reproject.hip): the previous
-// accumulator (wp x hp) resampled into the current view (w x h) -> out.  The
-// cameras are copied into the launch.
+// Temporal reprojection (reproject.hip): the
+// previous accumulator (wp x hp) resampled into the current view (w x h) ->
+// out.  The cameras are copied into the launch.  motion == nullptr: row 8.
+// Otherwise row 9: motion, motion_count records in device memory (a valid
+// address even for an empty table), is read per pixel through the guide's
+// shape index.
 hipError_t pt_launch_reproject(const float4* prev, const float4* prev_guides, uint32_t wp, uint32_t hp,
                                const pt_packed_camera* prev_camera, const float4* guides, uint32_t w, uint32_t h,
-                               const pt_packed_camera* camera, const pt_reproject_parameters* p, float4* out,
-                               hipStream_t st);
-// The same with a motion table: motion, motion_count
-// records in device memory, is read per pixel through the guide's shape index.
-hipError_t pt_launch_reproject_moving(const float4* prev, const float4* prev_guides, uint32_t wp, uint32_t hp,
-                                      const pt_packed_camera* prev_camera, const float4* guides, uint32_t w,
-                                      uint32_t h, const pt_packed_camera* camera, const pt_shape_motion* motion,
-                                      uint32_t motion_count, const pt_reproject_parameters* p, float4* out,
-                                      hipStream_t st);
+                               const pt_packed_camera* camera, const pt_shape_motion* motion, uint32_t motion_count,
+                               const pt_reproject_parameters* p, float4* out, hipStream_t st);
 // dst += src per component.
 hipError_t pt_launch_accumulate(float4* dst, const float4* src, uint64_t n, hipStream_t st);
 // compact: the completion-queue instantiation (ShadeTile), for scenes whose

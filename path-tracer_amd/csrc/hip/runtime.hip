@@ -325,6 +325,16 @@ int EndTimed(pt_device* dev, event_pair& ep)
     return 0;
 }
 
+// One launch, timed whenever the device profiles (the render loop's launches,
+// which are sampled and may cover several rounds, call the two halves).
+#define PT_TIMED(dev, KERNEL, launch)                               \
+    do {                                                            \
+        event_pair ep_{};                                           \
+        if (int b_ = BeginTimed(dev, KERNEL, ep_)) return b_;       \
+        PT_HIP(launch);                                             \
+        if (int d_ = EndTimed(dev, ep_)) return d_;                 \
+    } while (0)
+
 int CollectTimes(pt_device* dev)
 {
     if (dev->pending.empty()) return 0;
@@ -971,11 +981,9 @@ int ptRenderSampleBuffer(pt_device* d, pt_sample_buffer* b, const pt_resolve_par
     size_t n = (size_t)b->width * b->height;
     PT_HIP(b->display.alloc(n));
     PT_HIP(b->display8.alloc(n));
-    event_pair ep{};
-    if (int e = BeginTimed(d, PT_KERNEL_RESOLVE, ep)) return e;
-    PT_HIP(pt_launch_resolve(b->accum, (uint32_t)n, p->Brightness, p->ToneMappingMode, p->ToneMappingWhiteLevel,
-                             b->display.ptr, b->display8.ptr, d->stream));
-    if (int e = EndTimed(d, ep)) return e;
+    PT_TIMED(d, PT_KERNEL_RESOLVE,
+             pt_launch_resolve(b->accum, (uint32_t)n, p->Brightness, p->ToneMappingMode, p->ToneMappingWhiteLevel,
+                               b->display.ptr, b->display8.ptr, d->stream));
     b->resolved = true;
     return 0;
 }
@@ -1208,10 +1216,8 @@ int ptResetBasicRenderer(pt_device* d, pt_basic_renderer* r)
     r->grey = GreyForm(r);
     r->grey_blocked = false;
     r->slots.prob1 = r->grey ? r->prob1.ptr : nullptr;
-    event_pair ep{};
-    if (int e = BeginTimed(d, PT_KERNEL_RAYGEN, ep)) return e;
-    PT_HIP(pt_launch_raygen(r->scene->d, r->slots, Frame(r), Params(r, r->params.FrameIndex), d->stream));
-    if (int e = EndTimed(d, ep)) return e;
+    PT_TIMED(d, PT_KERNEL_RAYGEN,
+             pt_launch_raygen(r->scene->d, r->slots, Frame(r), Params(r, r->params.FrameIndex), d->stream));
     PT_HIP(hipMemsetAsync(r->done.ptr, 0, (size_t)(r->slots.n / 64 + 1) * 4, d->stream));
     r->rays = 0;
     return 0;
@@ -2036,10 +2042,8 @@ int ptRenderPreview(pt_device* d, pt_preview* c, const pt_preview_parameters* p)
         PT_HIP(c->spill.alloc((need - cap) * threads));
         spill = c->spill.ptr;
     }
-    event_pair ep{};
-    if (int e = BeginTimed(d, PT_KERNEL_PREVIEW, ep)) return e;
-    PT_HIP(pt_launch_preview(c->scene->d, p, spill, c->image.ptr, c->aov.ptr, c->query, c->observe.ptr, d->stream));
-    if (int e = EndTimed(d, ep)) return e;
+    PT_TIMED(d, PT_KERNEL_PREVIEW,
+             pt_launch_preview(c->scene->d, p, spill, c->image.ptr, c->aov.ptr, c->query, c->observe.ptr, d->stream));
     c->width = p->RenderSizeX;
     c->height = p->RenderSizeY;
     c->rendered = true;
@@ -2131,11 +2135,9 @@ int ptRenderDenoiseGuides(pt_device* d, pt_scene* s, pt_denoise_guides* g, uint3
         PT_HIP(g->spill.alloc((need - cap) * threads));
         spill = g->spill.ptr;
     }
-    event_pair ep{};
-    if (int e = BeginTimed(d, PT_KERNEL_GUIDES, ep)) return e;
-    PT_HIP(pt_launch_denoise_guides(s->d, camera_index, g->width, g->height, spill, g->records.ptr, g->observe.ptr,
-                                    d->stream));
-    if (int e = EndTimed(d, ep)) return e;
+    PT_TIMED(d, PT_KERNEL_GUIDES,
+             pt_launch_denoise_guides(s->d, camera_index, g->width, g->height, spill, g->records.ptr, g->observe.ptr,
+                                      d->stream));
     return 0;
 }
 
@@ -2166,10 +2168,13 @@ int ptSetDenoiseVariant(pt_denoise_guides* g, uint32_t variant)
     return 0;
 }
 
-// The kernel of iteration i (step 2^i).  Automatic mode takes the lattice
-// kernel at every step: measured at 1920x1080 and 3840x2160 it is 1.3 - 2 x
-// faster than the gather at each of the steps 1 .. 32, so the
-// choice does not depend on the iteration.
+// The kernel of iteration i (step 2^i), of the single-buffer and of the pair
+// filter.  Automatic mode takes the lattice kernel at every step: measured at
+// 1920x1080 and 3840x2160 it is 1.3 - 2 x faster than the gather at each of
+// the steps 1 .. 32, so the choice does not depend on the
+// iteration.  For the pair filter that started as this choice carried over,
+// then was measured on the pair filter itself, where the lattice is again
+// 1.2 - 2 x faster at each of the steps 1 .. 32.
 static bool DenoiseLattice(uint32_t variant, uint32_t /*iteration*/)
 {
     return variant != PT_DENOISE_VARIANT_GATHER;
@@ -2204,23 +2209,12 @@ int ptDenoiseSampleBuffer(pt_device* d, pt_sample_buffer* src, pt_denoise_guides
     const float4* in = src->accum;
     for (uint32_t i = 0; i < N; i++) {
         float4* out = ((N - 1 - i) & 1u) ? g->scratch.ptr : dst->accum;
-        event_pair ep{};
-        if (int e = BeginTimed(d, PT_KERNEL_DENOISE, ep)) return e;
-        PT_HIP(pt_launch_denoise(in, i == 0, g->records.ptr, g->width, g->height, p, i, DenoiseLattice(g->variant, i),
-                                 out, d->stream));
-        if (int e = EndTimed(d, ep)) return e;
+        PT_TIMED(d, PT_KERNEL_DENOISE,
+                 pt_launch_denoise(in, i == 0, g->records.ptr, g->width, g->height, p, i, DenoiseLattice(g->variant, i),
+                                   out, d->stream));
         in = out;
     }
     return 0;
-}
-
-// The pair filter's kernel of iteration i.  Automatic mode takes the lattice
-// kernel at every step: started as the single-buffer filter's choice carried
-// over, then measured on the pair kernels themselves, where the lattice is
-// again 1.2 - 2 x faster at each of the steps 1 .. 32.
-static bool DenoisePairLattice(uint32_t variant, uint32_t /*iteration*/)
-{
-    return variant != PT_DENOISE_VARIANT_GATHER;
 }
 
 int ptDenoiseSampleBufferPair(pt_device* d, pt_sample_buffer* a, pt_sample_buffer* b, pt_denoise_guides* g,
@@ -2251,65 +2245,26 @@ int ptDenoiseSampleBufferPair(pt_device* d, pt_sample_buffer* a, pt_sample_buffe
     // Image k (0: the prepare launch's, k: iteration k - 1's) is dst when an
     // even number of launches follow it, so the last one lands in dst.
     auto image = [&](uint32_t k) { return ((N - k) & 1u) ? g->scratch.ptr : dst->accum; };
-    {
-        event_pair ep{};
-        if (int e = BeginTimed(d, PT_KERNEL_DENOISE, ep)) return e;
-        PT_HIP(pt_launch_denoise_pair_prepare(a->accum, b->accum, g->records.ptr, g->width, g->height, N == 0,
-                                              image(0), d->stream));
-        if (int e = EndTimed(d, ep)) return e;
-    }
-    for (uint32_t i = 0; i < N; i++) {
-        event_pair ep{};
-        if (int e = BeginTimed(d, PT_KERNEL_DENOISE, ep)) return e;
-        PT_HIP(pt_launch_denoise_pair(image(i), g->records.ptr, g->width, g->height, p, i, i + 1 == N,
-                                      DenoisePairLattice(g->variant, i), image(i + 1), d->stream));
-        if (int e = EndTimed(d, ep)) return e;
-    }
+    PT_TIMED(d, PT_KERNEL_DENOISE,
+             pt_launch_denoise_pair_prepare(a->accum, b->accum, g->records.ptr, g->width, g->height, N == 0, image(0),
+                                            d->stream));
+    for (uint32_t i = 0; i < N; i++)
+        PT_TIMED(d, PT_KERNEL_DENOISE,
+                 pt_launch_denoise_pair(image(i), g->records.ptr, g->width, g->height, p, i, i + 1 == N,
+                                        DenoiseLattice(g->variant, i), image(i + 1), d->stream));
     return 0;
 }
 
-// --- temporal reprojection (reproject.hip) ---------------------
+// --- temporal reprojection (reproject.hip) --------------
 
-int ptReprojectSampleBuffer(pt_device* d, pt_sample_buffer* prev, pt_denoise_guides* pg, const pt_packed_camera* pc,
-                            pt_denoise_guides* g, const pt_packed_camera* c, const pt_reproject_parameters* p,
-                            pt_sample_buffer* dst)
-{
-    if (!d || !prev || !pg || !pc || !g || !c || !p || !dst) { SetError("null argument"); return -1; }
-    if (prev == dst) { SetError("reproject: prev and dst are the same sample buffer"); return -1; }
-    if (pg == g) { SetError("reproject: prev_guides and guides are the same object"); return -1; }
-    if (prev->dev != d || dst->dev != d || pg->dev != d || g->dev != d) {
-        SetError("reproject: objects of another device");
-        return -1;
-    }
-    if (prev->width != pg->width || prev->height != pg->height || dst->width != g->width || dst->height != g->height) {
-        SetError("reproject: size mismatch (prev %ux%u, prev_guides %ux%u, guides %ux%u, dst %ux%u)", prev->width,
-                 prev->height, pg->width, pg->height, g->width, g->height, dst->width, dst->height);
-        return -1;
-    }
-    if (!pt_reproject_parameters_ok(p)) {
-        SetError("reproject: bad parameters (NormalCosine in (-1, 1], DepthTolerance > 0, MinWeight in (0, 1], "
-                 "MaxHistory > 0)");
-        return -1;
-    }
-    PT_HIP(hipSetDevice(d->id));
-    event_pair ep{};
-    if (int e = BeginTimed(d, PT_KERNEL_REPROJECT, ep)) return e;
-    PT_HIP(pt_launch_reproject(prev->accum, pg->records.ptr, pg->width, pg->height, pc, g->records.ptr, g->width,
-                               g->height, c, p, dst->accum, d->stream));
-    if (int e = EndTimed(d, ep)) return e;
-    return 0;
-}
-
-// Row 9: the same checks, then the motion table's stream-ordered copy into the
-// device's own buffer and the moving-shape kernel.  Without a table (NULL, 0)
-// it is ptReprojectSampleBuffer.
-int ptReprojectSampleBufferMoving(pt_device* d, pt_sample_buffer* prev, pt_denoise_guides* pg,
-                                  const pt_packed_camera* pc, pt_denoise_guides* g, const pt_packed_camera* c,
-                                  const pt_shape_motion* motion, uint32_t motion_count,
-                                  const pt_reproject_parameters* p, pt_sample_buffer* dst)
+// Both entry points: the checks, then with a table (row 9) its stream-ordered
+// copy into the device's own buffer, then the launch.  Without one (NULL, 0)
+// it is row 8.
+static int Reproject(pt_device* d, pt_sample_buffer* prev, pt_denoise_guides* pg, const pt_packed_camera* pc,
+                     pt_denoise_guides* g, const pt_packed_camera* c, const pt_shape_motion* motion,
+                     uint32_t motion_count, const pt_reproject_parameters* p, pt_sample_buffer* dst)
 {
     if (!motion && motion_count) { SetError("reproject: %u motion records at a null pointer", motion_count); return -1; }
-    if (!motion) return ptReprojectSampleBuffer(d, prev, pg, pc, g, c, p, dst);
     if (!d || !prev || !pg || !pc || !g || !c || !p || !dst) { SetError("null argument"); return -1; }
     if (prev == dst) { SetError("reproject: prev and dst are the same sample buffer"); return -1; }
     if (pg == g) { SetError("reproject: prev_guides and guides are the same object"); return -1; }
@@ -2329,7 +2284,8 @@ int ptReprojectSampleBufferMoving(pt_device* d, pt_sample_buffer* prev, pt_denoi
     }
     PT_HIP(hipSetDevice(d->id));
     // Growing frees the old table; hipFree waits for the launches that read it.
-    PT_HIP(d->motion.alloc(motion_count));
+    // An empty table still has a device address: it is what selects row 9.
+    if (motion) PT_HIP(d->motion.alloc(motion_count));
     if (motion_count) {
         // The last call's upload may still be queued: it must have read the
         // pinned copy before this call overwrites it.
@@ -2348,12 +2304,26 @@ int ptReprojectSampleBufferMoving(pt_device* d, pt_sample_buffer* prev, pt_denoi
                               hipMemcpyHostToDevice, d->stream));
         PT_HIP(hipEventRecord(d->motion_copied, d->stream));
     }
-    event_pair ep{};
-    if (int e = BeginTimed(d, PT_KERNEL_REPROJECT, ep)) return e;
-    PT_HIP(pt_launch_reproject_moving(prev->accum, pg->records.ptr, pg->width, pg->height, pc, g->records.ptr, g->width,
-                                      g->height, c, d->motion.ptr, motion_count, p, dst->accum, d->stream));
-    if (int e = EndTimed(d, ep)) return e;
+    PT_TIMED(d, PT_KERNEL_REPROJECT,
+             pt_launch_reproject(prev->accum, pg->records.ptr, pg->width, pg->height, pc, g->records.ptr, g->width,
+                                 g->height, c, motion ? d->motion.ptr : nullptr, motion_count, p, dst->accum,
+                                 d->stream));
     return 0;
+}
+
+int ptReprojectSampleBuffer(pt_device* d, pt_sample_buffer* prev, pt_denoise_guides* pg, const pt_packed_camera* pc,
+                            pt_denoise_guides* g, const pt_packed_camera* c, const pt_reproject_parameters* p,
+                            pt_sample_buffer* dst)
+{
+    return Reproject(d, prev, pg, pc, g, c, nullptr, 0, p, dst);
+}
+
+int ptReprojectSampleBufferMoving(pt_device* d, pt_sample_buffer* prev, pt_denoise_guides* pg,
+                                  const pt_packed_camera* pc, pt_denoise_guides* g, const pt_packed_camera* c,
+                                  const pt_shape_motion* motion, uint32_t motion_count,
+                                  const pt_reproject_parameters* p, pt_sample_buffer* dst)
+{
+    return Reproject(d, prev, pg, pc, g, c, motion, motion_count, p, dst);
 }
 
 // --- frame statistics (stats.hip) ------------------------------
@@ -2394,11 +2364,9 @@ int ptComputeFrameStatistics(pt_device* d, pt_sample_buffer* a, pt_sample_buffer
     }
     const uint64_t n = (uint64_t)a->width * a->height;
     PT_HIP(hipMemsetAsync(d->stats, 0, sizeof(pt_frame_statistics), d->stream));
-    event_pair ep{};
-    if (int e = BeginTimed(d, PT_KERNEL_STATS, ep)) return e;
-    PT_HIP(pt_launch_frame_statistics(a->accum, b ? b->accum : nullptr, n, d->cu_count, StatsUniform(d->stats_variant),
-                                      d->stats, d->stream));
-    if (int e = EndTimed(d, ep)) return e;
+    PT_TIMED(d, PT_KERNEL_STATS,
+             pt_launch_frame_statistics(a->accum, b ? b->accum : nullptr, n, d->cu_count,
+                                        StatsUniform(d->stats_variant), d->stats, d->stream));
     pt_frame_statistics s;
     PT_HIP(hipMemcpyAsync(&s, d->stats, sizeof(s), hipMemcpyDeviceToHost, d->stream));
     PT_WAIT(d);
@@ -2421,10 +2389,8 @@ int ptAccumulateSampleBuffer(pt_device* d, pt_sample_buffer* dst, pt_sample_buff
         return -1;
     }
     PT_HIP(hipSetDevice(d->id));
-    event_pair ep{};
-    if (int e = BeginTimed(d, PT_KERNEL_STATS, ep)) return e;
-    PT_HIP(pt_launch_accumulate(dst->accum, src->accum, (uint64_t)dst->width * dst->height, d->stream));
-    if (int e = EndTimed(d, ep)) return e;
+    PT_TIMED(d, PT_KERNEL_STATS,
+             pt_launch_accumulate(dst->accum, src->accum, (uint64_t)dst->width * dst->height, d->stream));
     return 0;
 }
 

@@ -4,7 +4,8 @@
 // compared with: the same definition, the same per-tap arithmetic
 // (include/pt_denoise.h), the same tap order.  Single-threaded.
 // ptsDenoisePair is the same for the variance-guided filter over two half
-// renders and ptDenoiseSampleBufferPair.
+// renders and ptDenoiseSampleBufferPair.  The 5x5 loop
+// is one template; the two filters are its policies, as on the device.
 #include "../../../include/pt_scene.h"
 #include "../../../include/pt_denoise.h"
 
@@ -27,15 +28,65 @@ pt_denoise_pixel Pixel(const px4& c, const pt_denoise_guide& g)
     return p;
 }
 
-void Iterate(uint32_t W, uint32_t H, const px4* in, const pt_denoise_guide* guides, const pt_denoise_sigmas& sg,
-             uint32_t step, px4* out)
+struct pair_px { float x, y, z, v; bool filled; };   // colour, variance of its luminance
+
+// The two filters as policies of the one loop below: the image record (px),
+// whether it is empty, its colour, what is set up once per centre pixel, and
+// what a tap adds to the sums.
+struct single_filter {
+    using px = px4;
+    using sigmas = pt_denoise_sigmas;
+    struct sums { float x, y, z, w; };
+    static bool empty(const px& c) { return !(c.w > 0.0f); }
+    static px empty_px() { return {0, 0, 0, 0}; }
+    static px4 colour(const px& c) { return c; }
+    static float setup(const sigmas&, const px&) { return 0.0f; }
+    static void tap(sums& A, float h, const pt_denoise_pixel& p, const pt_denoise_pixel& q, float, const px&,
+                    const sigmas& sg)
+    {
+        const float w = pt_denoise_weight(h, &p, &q, &sg);
+        A.x = A.x + w * q.c.x;
+        A.y = A.y + w * q.c.y;
+        A.z = A.z + w * q.c.z;
+        A.w = A.w + w;
+    }
+    static px result(const sums& A) { return {A.x / A.w, A.y / A.w, A.z / A.w, 1.0f}; }
+};
+
+// The variance-guided filter over two half renders.
+struct pair_filter {
+    using px = pair_px;
+    using sigmas = pt_denoise_pair_sigmas;
+    struct sums { float x, y, z, w, v; };
+    static bool empty(const px& c) { return !c.filled; }
+    static px empty_px() { return {0, 0, 0, 0, false}; }
+    static px4 colour(const px& c) { return {c.x, c.y, c.z, 1.0f}; }
+    static float setup(const sigmas& sg, const px& c) { return pt_denoise_pair_scale(&sg, c.v); }
+    static void tap(sums& A, float h, const pt_denoise_pixel& p, const pt_denoise_pixel& q, float D, const px& c,
+                    const sigmas& sg)
+    {
+        const float w = pt_denoise_pair_weight(h, &p, &q, D, &sg);
+        A.x = A.x + w * q.c.x;
+        A.y = A.y + w * q.c.y;
+        A.z = A.z + w * q.c.z;
+        A.w = A.w + w;
+        A.v = A.v + (w * w) * c.v;
+    }
+    static px result(const sums& A) { return {A.x / A.w, A.y / A.w, A.z / A.w, A.v / (A.w * A.w), true}; }
+};
+
+// One a-trous iteration of filter F, in -> out.
+template <class F>
+void Iterate(uint32_t W, uint32_t H, const typename F::px* in, const pt_denoise_guide* guides,
+             const typename F::sigmas& sg, uint32_t step, typename F::px* out)
 {
     for (uint32_t y = 0; y < H; y++) {
         for (uint32_t x = 0; x < W; x++) {
             const size_t ip = (size_t)y * W + x;
-            if (!(in[ip].w > 0.0f)) { out[ip] = {0, 0, 0, 0}; continue; }
-            const pt_denoise_pixel p = Pixel(in[ip], guides[ip]);
-            float sx = 0.0f, sy = 0.0f, sz = 0.0f, sw = 0.0f;
+            if (F::empty(in[ip])) { out[ip] = F::empty_px(); continue; }
+            const pt_denoise_pixel p = Pixel(F::colour(in[ip]), guides[ip]);
+            const float C = F::setup(sg, in[ip]);
+            typename F::sums A{};
             for (int dy = -2; dy <= 2; dy++) {
                 const int64_t qy = (int64_t)y + (int64_t)dy * step;
                 if (qy < 0 || qy >= (int64_t)H) continue;
@@ -43,24 +94,16 @@ void Iterate(uint32_t W, uint32_t H, const px4* in, const pt_denoise_guide* guid
                     const int64_t qx = (int64_t)x + (int64_t)dx * step;
                     if (qx < 0 || qx >= (int64_t)W) continue;
                     const size_t iq = (size_t)qy * W + (size_t)qx;
-                    if (!(in[iq].w > 0.0f) || guides[iq].shape != p.shape) continue;
-                    const pt_denoise_pixel q = Pixel(in[iq], guides[iq]);
+                    if (F::empty(in[iq]) || guides[iq].shape != p.shape) continue;
+                    const pt_denoise_pixel q = Pixel(F::colour(in[iq]), guides[iq]);
                     const float h = pt_denoise_k(dx + 2) * pt_denoise_k(dy + 2);
-                    const float w = pt_denoise_weight(h, &p, &q, &sg);
-                    sx = sx + w * q.c.x;
-                    sy = sy + w * q.c.y;
-                    sz = sz + w * q.c.z;
-                    sw = sw + w;
+                    F::tap(A, h, p, q, C, in[iq], sg);
                 }
             }
-            out[ip] = {sx / sw, sy / sw, sz / sw, 1.0f};
+            out[ip] = F::result(A);
         }
     }
 }
-
-// --- the variance-guided filter over two half renders ---
-
-struct pair_px { float x, y, z, v; bool filled; };   // colour, variance of its luminance
 
 // c_0 and the prefiltered variance v_0 of S = A + B.
 void PairPrepare(uint32_t W, uint32_t H, const float* A, const float* B, const pt_denoise_guide* guides, pair_px* out)
@@ -95,39 +138,6 @@ void PairPrepare(uint32_t W, uint32_t H, const float* A, const float* B, const p
     }
 }
 
-void PairIterate(uint32_t W, uint32_t H, const pair_px* in, const pt_denoise_guide* guides,
-                 const pt_denoise_pair_sigmas& sg, uint32_t step, pair_px* out)
-{
-    for (uint32_t y = 0; y < H; y++) {
-        for (uint32_t x = 0; x < W; x++) {
-            const size_t ip = (size_t)y * W + x;
-            if (!in[ip].filled) { out[ip] = {0, 0, 0, 0, false}; continue; }
-            const pt_denoise_pixel p = Pixel({in[ip].x, in[ip].y, in[ip].z, 1.0f}, guides[ip]);
-            const float D = pt_denoise_pair_scale(&sg, in[ip].v);
-            float sx = 0.0f, sy = 0.0f, sz = 0.0f, sw = 0.0f, sv = 0.0f;
-            for (int dy = -2; dy <= 2; dy++) {
-                const int64_t qy = (int64_t)y + (int64_t)dy * step;
-                if (qy < 0 || qy >= (int64_t)H) continue;
-                for (int dx = -2; dx <= 2; dx++) {
-                    const int64_t qx = (int64_t)x + (int64_t)dx * step;
-                    if (qx < 0 || qx >= (int64_t)W) continue;
-                    const size_t iq = (size_t)qy * W + (size_t)qx;
-                    if (!in[iq].filled || guides[iq].shape != p.shape) continue;
-                    const pt_denoise_pixel q = Pixel({in[iq].x, in[iq].y, in[iq].z, 1.0f}, guides[iq]);
-                    const float h = pt_denoise_k(dx + 2) * pt_denoise_k(dy + 2);
-                    const float w = pt_denoise_pair_weight(h, &p, &q, D, &sg);
-                    sx = sx + w * q.c.x;
-                    sy = sy + w * q.c.y;
-                    sz = sz + w * q.c.z;
-                    sw = sw + w;
-                    sv = sv + (w * w) * in[iq].v;
-                }
-            }
-            out[ip] = {sx / sw, sy / sw, sz / sw, sv / (sw * sw), true};
-        }
-    }
-}
-
 }  // namespace
 
 extern "C" int ptsDenoisePair(uint32_t width, uint32_t height, const float* accum_a, const float* accum_b,
@@ -143,7 +153,7 @@ extern "C" int ptsDenoisePair(uint32_t width, uint32_t height, const float* accu
         PairPrepare(width, height, accum_a, accum_b, guides, a.data());
         const pt_denoise_pair_sigmas sg = pt_denoise_pair_make_sigmas(params);
         for (uint32_t i = 0; i < params->Iterations; i++) {
-            PairIterate(width, height, a.data(), guides, sg, 1u << i, b.data());
+            Iterate<pair_filter>(width, height, a.data(), guides, sg, 1u << i, b.data());
             a.swap(b);
         }
         for (size_t i = 0; i < n; i++) {
@@ -171,7 +181,8 @@ extern "C" int ptsDenoise(uint32_t width, uint32_t height, const float* accum_rg
             else a[i] = {0, 0, 0, 0};
         }
         for (uint32_t i = 0; i < params->Iterations; i++) {
-            Iterate(width, height, a.data(), guides, pt_denoise_iteration_sigmas(params, i), 1u << i, b.data());
+            Iterate<single_filter>(width, height, a.data(), guides, pt_denoise_iteration_sigmas(params, i), 1u << i,
+                                   b.data());
             a.swap(b);
         }
         std::memcpy(out_rgba, a.data(), n * sizeof(px4));

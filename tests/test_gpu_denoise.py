@@ -16,10 +16,11 @@ import resolve_restatement
 pytestmark = pytest.mark.gpu
 
 NONE = 0xFFFFFFFF
-# 40x24: smaller than one lattice block's window for steps >= 2; 67x45: odd,
+# 5x3: smaller than one tile, the step exceeds both dimensions from iteration
+# 3 on, and every column is a residue class of its own; 40x24: smaller than one lattice block's window for steps >= 2; 67x45: odd,
 # a partial tile on both edges, residue classes of unequal size; 130x70: more
 # than one block per residue class at step 4.
-SIZES = [(40, 24), (67, 45), (130, 70)]
+SIZES = [(5, 3), (40, 24), (67, 45), (130, 70)]
 ITERATIONS = [1, 3, 5, 6]
 
 
