@@ -34,7 +34,9 @@
  * those two half renders (ptDenoiseSampleBufferPair), and temporal
  * reprojection of an accumulator into a new view (ptReprojectSampleBuffer),
  * which keeps a frame's history across a camera move
- * (ptReprojectSampleBufferMoving: and across an object move).
+ * (ptReprojectSampleBufferMoving: and across an object move), and rounds on a
+ * chosen set of 16 x 16 tiles (ptSetBasicRendererActiveTiles) with the
+ * per-tile statistics that choose them (ptComputeTileStatistics).
  *
  * Conventions: creators return NULL on failure and set ptGetLastError();
  * other calls return 0 on success or a non-zero status (HIP / RCCL error
@@ -108,7 +110,7 @@ enum {
     PT_KERNEL_ROUNDS  = 6,   /* a round batch: several rounds of every tile in one launch */
     PT_KERNEL_DENOISE = 7,   /* one a-trous iteration of ptDenoiseSampleBuffer */
     PT_KERNEL_GUIDES  = 8,   /* ptRenderDenoiseGuides */
-    PT_KERNEL_STATS   = 9,   /* ptComputeFrameStatistics' pass and ptAccumulateSampleBuffer's add */
+    PT_KERNEL_STATS   = 9,   /* ptComputeFrameStatistics' and ptComputeTileStatistics' passes, ptAccumulateSampleBuffer's add */
     PT_KERNEL_REPROJECT = 10, /* ptReprojectSampleBuffer, ptReprojectSampleBufferMoving */
     PT_KERNEL_COUNT   = 11,
 };
@@ -280,6 +282,38 @@ int                ptGetBasicRendererClassLists(const pt_basic_renderer* rendere
 int                ptSetBasicRendererSplit(pt_basic_renderer* renderer, uint32_t groups);
 int                ptGetBasicRendererSplit(const pt_basic_renderer* renderer, uint32_t* groups, uint32_t* timed_tiles,
                                            uint32_t* tiles);
+/* Active tile set (no reference counterpart): the rounds
+ * that follow run on the chosen 16 x 16 tiles only.  A full-frame renderer
+ * numbers its tiles row-major: tile (tx, ty) covers the pixels [16 tx, 16 tx +
+ * 16) x [16 ty, 16 ty + 16) clipped to the image and has index ty * tiles_x +
+ * tx, tiles_x = ceil(width / 16) -- pt_tile_statistics' numbering.
+ * mask[t] != 0: tile t takes part; mask == NULL with tiles == 0: every tile
+ * (the default).  The mask is copied.
+ *   - ptRunBasicRenderer and ptRunBasicRendererRounds advance FrameIndex as
+ *     before; their launches cover the active tiles.  Nothing of an inactive
+ *     tile is written: slot records, TileOrder words, outcome and done words,
+ *     accumulator pixels.  After the same calls from the same state an active
+ *     tile's slots and pixels equal an unmasked renderer's bit for bit, in
+ *     every scheduling mode (separate launches, fused rounds, round batches,
+ *     tile groups).  An all-zero mask launches nothing; an all-ones mask gives
+ *     the bits of no mask.
+ *   - ptResetBasicRenderer keeps the mask and still restarts every tile's
+ *     paths.  State reads and writes cover the whole frame.  (A change of the
+ *     path record form after a scene update converts every tile's records.)
+ *   - ptGetStats' rays grow by the active tiles' valid slots per round.
+ *   - The automatic rules of tile groups and fused rounds count the active
+ *     tiles.  Class lists are off while a mask is set
+ *     (ptGetBasicRendererClassLists reports 0), and the longest-first re-sort
+ *     of the dispatch order rests: active tiles run in natural order.
+ *   - Setting or clearing a mask waits for the device.
+ * Fails, launching nothing and leaving the set as it was, on a NULL device or
+ * renderer, a partitioned or multi-stream renderer, tiles different from the
+ * renderer's tile count, or a NULL mask with tiles > 0.  ptRenderFrame fails
+ * while a mask is set.  ptGetBasicRendererActiveTiles: the tiles the next
+ * round launches and all tiles; either pointer may be NULL. */
+int                ptSetBasicRendererActiveTiles(pt_device* device, pt_basic_renderer* renderer, const uint8_t* mask,
+                                                 uint32_t tiles);
+int                ptGetBasicRendererActiveTiles(const pt_basic_renderer* renderer, uint32_t* active, uint32_t* tiles);
 /* OpenPBR shading (opt-in extension, no reference counterpart): 0 (default)
  * = an OpenPBR hit ends its path with no contribution, as in the reference,
  * whose integrator does not compile its OpenPBR BSDF (scene.glsl.inc:685);
@@ -496,6 +530,20 @@ int  ptReprojectSampleBufferMoving(pt_device* device, pt_sample_buffer* prev, pt
  * out, on b == a, and on a or b of another device or b of another size. */
 int  ptComputeFrameStatistics(pt_device* device, pt_sample_buffer* a, pt_sample_buffer* b,
                               pt_frame_statistics* out);
+/* Per-tile statistics (no reference counterpart): the
+ * classes and the pair rule of the frame statistics counted per 16 x 16 tile
+ * in one device pass, the data an active tile set is chosen from.  out holds
+ * ceil(width / 16) * ceil(height / 16) records, tile (tx, ty) at ty *
+ * ceil(width / 16) + tx (ptSetBasicRendererActiveTiles' numbering).  Without b
+ * pair and over are 0; with b the classes and counts describe a + b.  over
+ * counts the pair pixels whose relative half-difference r exceeds
+ * noise_threshold.  Blocks, like ptComputeFrameStatistics; one launch,
+ * counted under PT_KERNEL_STATS.  Equals ptsTileStatistics (pt_scene.h) bit
+ * for bit.  Fails, launching nothing and leaving out untouched, on
+ * ptComputeFrameStatistics' errors and on a noise_threshold that is NaN or
+ * negative. */
+int  ptComputeTileStatistics(pt_device* device, pt_sample_buffer* a, pt_sample_buffer* b, float noise_threshold,
+                             pt_tile_statistics* out);
 /* Enqueues dst's accumulator += src's, each component in binary32: combines
  * two halves without a host round trip.  src is not written.  Fails,
  * launching nothing, on a NULL argument, dst == src, or buffers of different

@@ -270,9 +270,27 @@ typedef struct pt_frame_statistics {
     uint32_t noise_histogram[PT_STATS_BINS];       /* pt_stats_bin(r), r = |Y_A - Y_B| / (Y_A + Y_B) */
 } pt_frame_statistics;
 
+/* Per-tile statistics (no reference counterpart): row
+ * 6's classes and pair rule counted per 16 x 16 tile.  Tile (tx, ty) covers
+ * the pixels [16 tx, 16 tx + 16) x [16 ty, 16 ty + 16) clipped to the image
+ * and has index ty * ceil(width / 16) + tx, a full-frame renderer's tile
+ * number.  Computed by ptComputeTileStatistics (pt_api.h) and
+ * ptsTileStatistics (pt_scene.h), bit for bit alike.
+ * filled + empty + nonfinite = the tile's pixels. */
+#define PT_TILE_SIZE 16
+
+typedef struct pt_tile_statistics {
+    uint32_t filled, empty, nonfinite; /* pt_stats_classify of a, or of a + b (each component added in binary32) */
+    uint32_t pair;                     /* filled in a and in b and pt_stats_pair_noise(Y_A, Y_B, &r) returns 1 */
+    uint32_t over;                     /* of those, r > noise_threshold */
+    float    min_count, max_count;     /* the classified accumulator's .w over filled pixels; 0, 0 without any */
+    uint32_t reserved;                 /* 0 */
+} pt_tile_statistics;
+
 #ifdef __cplusplus
 }
 static_assert(sizeof(pt_frame_statistics) == 2120, "frame_statistics");
+static_assert(sizeof(pt_tile_statistics) == 32, "tile_statistics");
 static_assert(sizeof(pt_denoise_guide) == 32, "denoise_guide");
 static_assert(sizeof(pt_denoise_parameters) == 20, "denoise_parameters");
 static_assert(sizeof(pt_denoise_pair_parameters) == 20, "denoise_pair_parameters");

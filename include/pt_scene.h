@@ -254,6 +254,14 @@ int  ptsCentralCameraRay(const pt_packed_camera* camera, uint32_t x, uint32_t y,
  * Single-threaded. */
 int  ptsFrameStatistics(uint32_t width, uint32_t height, const float* accum_a, const float* accum_b,
                         pt_frame_statistics* out);
+/* Per-tile statistics on the host (pt_tile_statistics in
+ * pt_packed.h): out holds ceil(width / 16) * ceil(height / 16) records, tile
+ * (tx, ty) at ty * ceil(width / 16) + tx.  accum_b NULL: pair and over are 0.
+ * Equals ptComputeTileStatistics (pt_api.h) bit for bit.  Returns non-zero,
+ * leaving out untouched, on a NULL accum_a or out, an empty image, accum_b ==
+ * accum_a, or a noise_threshold that is NaN or negative.  Single-threaded. */
+int  ptsTileStatistics(uint32_t width, uint32_t height, const float* accum_a, const float* accum_b,
+                       float noise_threshold, pt_tile_statistics* out);
 /* pt_stats.h's bin function and double helpers as library calls (for callers
  * that cannot include the header): the bin of a value; the lower edge of bin
  * 0..256 (0 outside); the percentile bin of a 256-bin histogram (-1 when

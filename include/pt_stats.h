@@ -61,6 +61,46 @@ PT_HD int pt_stats_pair_noise(float Ya, float Yb, float* r)
     return 1;
 }
 
+/* --- per tile --------------------------------------------- */
+
+/* One pixel's share of its tile's pt_tile_statistics: bit flags, and the
+ * classified accumulator's .w bits for a filled pixel.  has_b == 0: the class
+ * of a alone, no pair.  Otherwise the class of a + b and the pair rule on the
+ * two halves, as pt_frame_statistics counts them. */
+enum {
+    PT_TILE_PX_FILLED    = 1,
+    PT_TILE_PX_EMPTY     = 2,
+    PT_TILE_PX_NONFINITE = 4,
+    PT_TILE_PX_PAIR      = 8,
+    PT_TILE_PX_OVER      = 16,
+};
+
+PT_HD uint32_t pt_tile_stats_pixel(const float a[4], const float b[4], int has_b, float noise_threshold,
+                                   uint32_t* w_bits)
+{
+    float p[4] = {a[0], a[1], a[2], a[3]};
+    uint32_t flags = 0;
+    if (has_b) {
+        float Ya = 0.0f, Yb = 0.0f, r = 0.0f;
+        for (int k = 0; k < 4; k++) p[k] = a[k] + b[k];
+        if (pt_stats_classify(a[0], a[1], a[2], a[3], &Ya) == PT_STATS_FILLED &&
+            pt_stats_classify(b[0], b[1], b[2], b[3], &Yb) == PT_STATS_FILLED && pt_stats_pair_noise(Ya, Yb, &r)) {
+            flags |= PT_TILE_PX_PAIR;
+            if (r > noise_threshold) flags |= PT_TILE_PX_OVER;
+        }
+    }
+    float Y = 0.0f;
+    const int c = pt_stats_classify(p[0], p[1], p[2], p[3], &Y);
+    *w_bits = 0;
+    if (c == PT_STATS_NONFINITE) return flags | PT_TILE_PX_NONFINITE;
+    if (c == PT_STATS_EMPTY) return flags | PT_TILE_PX_EMPTY;
+    *w_bits = pt_f2u(p[3]);            /* w > 0: orders as its bits */
+    return flags | PT_TILE_PX_FILLED;
+}
+
+/* A usable threshold: not NaN and not negative (+infinity: nothing is over). */
+PT_HD int pt_tile_stats_threshold_ok(float noise_threshold) { return noise_threshold >= 0.0f; }
+
 /* --- reading the result (host, double) ------------------------------------------ */
 
 /* Lower edge of bin b, 0 <= b <= 256 (256: the upper edge of the last bin):

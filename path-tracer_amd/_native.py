@@ -131,6 +131,13 @@ class pt_frame_statistics(C.Structure):
     ]
 
 
+# pt_tile_statistics (include/pt_packed.h): one 32-byte record per 16 x 16 tile.
+TILE_SIZE = 16
+TILE_STATS_DTYPE = np.dtype([("filled", "<u4"), ("empty", "<u4"), ("nonfinite", "<u4"), ("pair", "<u4"),
+                             ("over", "<u4"), ("min_count", "<f4"), ("max_count", "<f4"), ("reserved", "<u4")])
+assert TILE_STATS_DTYPE.itemsize == 32
+
+
 class pt_packed_transform(C.Structure):
     _fields_ = [("To", C.c_float * 16), ("From", C.c_float * 16)]
 
@@ -236,7 +243,7 @@ KERNEL_DENOISE = 7   # one a-trous iteration (PT_KERNEL_DENOISE)
 KERNEL_GUIDES = 8    # ptRenderDenoiseGuides (PT_KERNEL_GUIDES)
 DENOISE_MAX_ITERATIONS = 8
 DENOISE_VARIANT_AUTO, DENOISE_VARIANT_GATHER, DENOISE_VARIANT_LATTICE = 0, 1, 2
-KERNEL_STATS = 9     # the frame statistics pass and the sample-buffer add (PT_KERNEL_STATS)
+KERNEL_STATS = 9     # the frame and tile statistics passes and the sample-buffer add (PT_KERNEL_STATS)
 STATS_VARIANT_AUTO, STATS_VARIANT_PLAIN, STATS_VARIANT_UNIFORM = 0, 1, 2
 KERNEL_REPROJECT = 10   # ptReprojectSampleBuffer and ptReprojectSampleBufferMoving (PT_KERNEL_REPROJECT)
 
@@ -311,6 +318,7 @@ SCENE_API = {
                                   C.POINTER(pt_packed_camera), _vp, _u32, C.POINTER(pt_reproject_parameters), _fptr]),
     "ptsCentralCameraRay": (_i32, [C.POINTER(pt_packed_camera), _u32, _u32, _u32, _u32, _fptr, _fptr]),
     "ptsFrameStatistics": (_i32, [_u32, _u32, _fptr, _fptr, C.POINTER(pt_frame_statistics)]),
+    "ptsTileStatistics": (_i32, [_u32, _u32, _fptr, _fptr, _f32, _vp]),
     "ptsStatsBin": (_i32, [C.c_float]),
     "ptsStatsBinEdge": (C.c_double, [_i32]),
     "ptsStatsPercentileBin": (_i32, [_u32ptr, C.c_double]),
@@ -386,6 +394,9 @@ HIP_API = {
                                              C.POINTER(pt_packed_camera), _vp, _u32,
                                              C.POINTER(pt_reproject_parameters), _vp]),
     "ptComputeFrameStatistics": (_i32, [_vp, _vp, _vp, C.POINTER(pt_frame_statistics)]),
+    "ptComputeTileStatistics": (_i32, [_vp, _vp, _vp, _f32, _vp]),
+    "ptSetBasicRendererActiveTiles": (_i32, [_vp, _vp, _vp, _u32]),
+    "ptGetBasicRendererActiveTiles": (_i32, [_vp, _u32ptr, _u32ptr]),
     "ptAccumulateSampleBuffer": (_i32, [_vp, _vp, _vp]),
     "ptSetFrameStatisticsVariant": (_i32, [_vp, _u32]),
     "ptCheckFastDivision": (_i32, [_vp, C.c_uint64, _u32, C.POINTER(C.c_uint64)]),

@@ -144,6 +144,12 @@ hipError_t pt_launch_denoise_pair(const float4* in, const float4* guides, uint32
 uint32_t pt_frame_statistics_grid(uint64_t n, uint32_t cu_count);
 hipError_t pt_launch_frame_statistics(const float4* a, const float4* b, uint64_t n, uint32_t cu_count, bool uniform,
                                       pt_frame_statistics* out, hipStream_t st);
+// Per-tile statistics (stats.hip): one record per 16 x 16
+// tile of a, or of a + b with the pair counts (b != nullptr), written to out
+// (ceil(width / 16) * ceil(height / 16) records, row-major).  One block per
+// tile; every record is written whole, so out needs no clearing.
+hipError_t pt_launch_tile_statistics(const float4* a, const float4* b, uint32_t width, uint32_t height,
+                                     float threshold, pt_tile_statistics* out, hipStream_t st);
 // Temporal reprojection (reproject.hip): the
 // previous accumulator (wp x hp) resampled into the current view (w x h) ->
 // out.  The cameras are copied into the launch.  motion == nullptr: row 8.

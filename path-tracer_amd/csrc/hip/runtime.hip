@@ -11,6 +11,7 @@
 #include "../../../include/pt_api.h"
 #include "../../../include/pt_denoise.h"
 #include "../../../include/pt_reproject.h"
+#include "../../../include/pt_stats.h"
 
 #include <rccl/rccl.h>
 
@@ -110,6 +111,9 @@ struct pt_device {
     // call, cleared on `stream` before every launch.
     pt_frame_statistics* stats = nullptr;
     uint32_t stats_variant = PT_STATS_VARIANT_AUTO;
+    // ptComputeTileStatistics' records on the device: grown on demand, every
+    // record rewritten by each launch.
+    dbuf<pt_tile_statistics> tile_stats;
     // ptReprojectSampleBufferMoving's motion table on the device: grown on
     // demand, rewritten on `stream` before every launch that reads it, from a
     // pinned copy of the caller's table (so the caller's memory is done with
@@ -215,6 +219,14 @@ struct pt_basic_renderer {
     uint32_t split = 0;                 // tile groups of consecutive rounds (ptSetBasicRendererSplit): 0 auto, 1 off
     dbuf<uint32_t> guard;               // guarded rounds' {stop, rounds run} (ptRenderFrame)
     uint32_t order_groups = 1;          // the group structure the order array holds (tile_order_kernel)
+    // Active tile set (ptSetBasicRendererActiveTiles): one byte per tile, empty
+    // = every tile.  While set, each group's segment of the order array holds
+    // the group's active tiles first, in natural order (WriteOrder), and the
+    // rounds' launches cover only those.
+    std::vector<uint8_t> mask;
+    uint32_t active_tiles = 0;          // tiles set in mask
+    uint64_t active_slots = 0;          // their valid slots: the paths of one masked round
+    uint32_t group_active[PT_MAX_SPLIT] = {};   // active tiles of each of the order_groups groups
     uint64_t pixels = 0;                // image pixels owned
     uint32_t streams = 1;               // path streams per owned pixel (ptCreateBasicRendererStreams)
     uint32_t stream_tiles = 0;          // tiles per stream
@@ -561,6 +573,7 @@ void ptDestroyDevice(pt_device* d)
     }
     if (d->fork_event) (void)hipEventDestroy(d->fork_event);
     if (d->stats) (void)hipFree(d->stats);
+    d->tile_stats.release();
     d->motion.release();
     if (d->motion_host) (void)hipHostFree(d->motion_host);
     if (d->motion_copied) (void)hipEventDestroy(d->motion_copied);
@@ -1243,6 +1256,24 @@ static bool ShadeCompact(const pt_basic_renderer* r)
            r->scene->d.g.SkyboxSamplingProbability > 0.0f || r->params.PathTerminationProbability > 0.0f;
 }
 
+// Active tile set (ptSetBasicRendererActiveTiles).  The kernels of a round
+// take their tile from order[blockIdx.x] and their grid from tile_count, so a
+// round over a subset is a launch whose tile_count is the subset's size over
+// an order array that lists the subset first: the view tile groups use.
+static bool Masked(const pt_basic_renderer* r) { return !r->mask.empty(); }
+
+// The paths one round traces.
+static uint64_t RoundSlots(const pt_basic_renderer* r) { return Masked(r) ? r->active_slots : r->valid_slots; }
+
+// The slots of a single-stream round: with a mask, the active tiles at the
+// head of the order array (which must hold one group: EnsureOrderGroups(1)).
+static ptd::dslots ActiveSlots(const pt_basic_renderer* r)
+{
+    ptd::dslots L = r->slots;
+    if (Masked(r)) L.tile_count = r->active_tiles;
+    return L;
+}
+
 static bool RoundFused(const pt_basic_renderer* r, const ptd::dslots& g)
 {
     const int mode = r->fused;
@@ -1291,6 +1322,7 @@ static int ClassListBuffers(pt_device* d, pt_basic_renderer* r, uint32_t K)
 }
 
 static bool ClassListRounds(const pt_basic_renderer* r);
+static int EnsureOrderGroups(pt_device* d, pt_basic_renderer* r, uint32_t K);
 
 // Class-pure shade of one single-stream round over every tile (the
 // renderer's rounds outside tile groups: Run(2), single rounds, guarded
@@ -1318,12 +1350,21 @@ int ptRunBasicRenderer(pt_device* d, pt_basic_renderer* r, uint32_t rounds)
     if (!d) { SetError("null device"); return -1; }
     if (CheckReady(r) != 0) return -1;
     PT_HIP(hipSetDevice(d->id));
+    if (Masked(r) && r->active_tiles == 0) {   // nothing to launch: the call still takes its seed
+        r->params.FrameIndex += 1;
+        return 0;
+    }
     if (int e = EnsureSpill(r)) return e;
     if (int e = SyncRecordForm(d, r)) return e;
+    if (Masked(r))
+        if (int e = EnsureOrderGroups(d, r, 1)) return e;
     r->params.FrameIndex += 1;
     ptd::dparams P = Params(r, r->params.FrameIndex);
     ptd::dframe F = Frame(r);
-    const ptd::dslots& L = r->slots;
+    const ptd::dslots L = ActiveSlots(r);
+    // A masked renderer keeps the natural order (no longest-first re-sort:
+    // tile_order_kernel permutes whole segments).
+    const bool resort = !Masked(r);
     const bool fused = RoundFused(r, L);
     // Run(R >= 2) where round batches apply (RunRounds' rule): the R rounds
     // with the one seed as batches of the rounds kernel (seed_step 0), one
@@ -1342,9 +1383,9 @@ int ptRunBasicRenderer(pt_device* d, pt_basic_renderer* r, uint32_t rounds)
             if (int e = BeginTimed(d, PT_KERNEL_ROUNDS, ep, sampled, n)) return e;
             PT_HIP(pt_launch_rounds(r->scene->d, L, F, Pb, ShadeMats(r), d->stream));
             if (int e = EndTimed(d, ep)) return e;
-            for (uint32_t g = 0; g < r->order_groups; g++)
+            for (uint32_t g = 0; resort && g < r->order_groups; g++)
                 PT_HIP(pt_launch_tile_order(L, d->stream, r->order_groups, g));
-            r->rays += r->valid_slots * n;
+            r->rays += RoundSlots(r) * n;
             left -= n;
         }
         return 0;
@@ -1354,7 +1395,7 @@ int ptRunBasicRenderer(pt_device* d, pt_basic_renderer* r, uint32_t rounds)
         const bool sampled = d->profiling && (d->run_tick++ % d->profile_period) == 0;
         // Tiles keep their relative cost for many rounds: re-sort every
         // TILE_ORDER_PERIOD rounds (one small launch).
-        const bool sort = L.order && (r->order_tick++ % TILE_ORDER_PERIOD) == 0;
+        const bool sort = L.order && (r->order_tick++ % TILE_ORDER_PERIOD) == 0 && resort;
         event_pair ep{};
         if (fused) {
             if (int e = BeginTimed(d, PT_KERNEL_ROUND, ep, sampled)) return e;
@@ -1374,7 +1415,7 @@ int ptRunBasicRenderer(pt_device* d, pt_basic_renderer* r, uint32_t rounds)
         }
         if (sort)
             for (uint32_t g = 0; g < r->order_groups; g++) PT_HIP(pt_launch_tile_order(L, d->stream, r->order_groups, g));
-        r->rays += r->valid_slots;
+        r->rays += RoundSlots(r);
     }
     return 0;
 }
@@ -1397,9 +1438,11 @@ constexpr uint32_t SPLIT_AUTO_GROUPS = 3;
 
 static uint32_t SplitGroups(const pt_basic_renderer* r)
 {
-    const ptd::dslots& L = r->slots;
-    if (!L.order || L.tile_count < 2 || r->split == 1) return 1;
-    if (r->split >= 2) return std::min(r->split, L.tile_count);
+    // The groups partition every tile of the renderer, masked or not (group
+    // t % K); the automatic mode's rules look at the tiles a round launches.
+    const ptd::dslots L = ActiveSlots(r);
+    if (!L.order || r->slots.tile_count < 2 || r->split == 1) return 1;
+    if (r->split >= 2) return std::min(r->split, r->slots.tile_count);
     return (!RoundFused(r, L) && L.tile_count >= SPLIT_MIN_TILES) ? SPLIT_AUTO_GROUPS : 1u;
 }
 
@@ -1411,27 +1454,49 @@ static uint32_t SplitGroups(const pt_basic_renderer* r)
 // the tile-local shade.
 static bool ClassLists(const pt_basic_renderer* r)
 {
-    return r->class_lists != 1 && r->scene->d.mat_classes != 0 && pt_class_lists_supported(ShadeMats(r));
+    // class_list_kernel derives a group's tiles arithmetically: off under a mask.
+    return r->class_lists != 1 && !Masked(r) && r->scene->d.mat_classes != 0 &&
+           pt_class_lists_supported(ShadeMats(r));
 }
 
 // Rounds of this renderer shade through class lists (tile groups and
 // single-stream rounds alike).
 static bool ClassListRounds(const pt_basic_renderer* r) { return SplitGroups(r) > 1 && ClassLists(r); }
 
+// Rewrites the dispatch order for K groups, each group's tiles in its own
+// segment in natural order; with an active tile set, a segment's active tiles
+// first (group_active of them), the inactive ones behind.  Waits for the
+// device first: queued launches may still read the array.
+static int WriteOrder(pt_device* d, pt_basic_renderer* r, uint32_t K)
+{
+    if (!r->slots.order) return 0;
+    const uint32_t T = r->slots.tile_count;
+    std::vector<uint32_t> order(T);
+    uint32_t i = 0;
+    for (uint32_t g = 0; g < PT_MAX_SPLIT; g++) r->group_active[g] = 0;
+    for (uint32_t g = 0; g < K; g++) {
+        const uint32_t n = pt_tile_group_count(T, K, g);
+        for (uint32_t pass = 0; pass < (Masked(r) ? 2u : 1u); pass++) {
+            for (uint32_t j = 0; j < n; j++) {
+                const uint32_t t = pt_tile_group_tile(T, K, g, j);
+                if (Masked(r) && (r->mask[t] != 0) != (pass == 0)) continue;
+                order[i++] = t;
+                if (Masked(r) && pass == 0) r->group_active[g]++;
+            }
+        }
+    }
+    PT_WAIT(d);
+    PT_HIP(hipMemcpy(r->order.ptr, order.data(), (size_t)T * 4, hipMemcpyHostToDevice));
+    r->order_groups = K;
+    return 0;
+}
+
 // The dispatch order holds each group's tiles in its own segment; a change of
 // K restarts it from the natural order of each group.
 static int EnsureOrderGroups(pt_device* d, pt_basic_renderer* r, uint32_t K)
 {
     if (r->order_groups == K || !r->slots.order) return 0;
-    const uint32_t T = r->slots.tile_count;
-    std::vector<uint32_t> order(T);
-    uint32_t i = 0;
-    for (uint32_t g = 0; g < K; g++)
-        for (uint32_t j = 0; j < pt_tile_group_count(T, K, g); j++) order[i++] = pt_tile_group_tile(T, K, g, j);
-    PT_WAIT(d);
-    PT_HIP(hipMemcpy(r->order.ptr, order.data(), (size_t)T * 4, hipMemcpyHostToDevice));
-    r->order_groups = K;
-    return 0;
+    return WriteOrder(d, r, K);
 }
 
 static int EnsureGroupStreams(pt_device* d, uint32_t K)
@@ -1463,7 +1528,7 @@ static int RunRoundsSplit(pt_device* d, pt_basic_renderer* r, uint64_t k, uint32
     for (uint32_t g = 0; g < K; g++) {
         G[g] = r->slots;
         G[g].order = r->slots.order + pt_tile_group_start(r->slots.tile_count, K, g);
-        G[g].tile_count = pt_tile_group_count(r->slots.tile_count, K, g);
+        G[g].tile_count = Masked(r) ? r->group_active[g] : pt_tile_group_count(r->slots.tile_count, K, g);
         S[g] = g ? d->group_stream[g - 1] : d->stream;
     }
     const bool lists = ClassLists(r);
@@ -1481,8 +1546,9 @@ static int RunRoundsSplit(pt_device* d, pt_basic_renderer* r, uint64_t k, uint32
             r->params.FrameIndex += 1;
             const ptd::dparams P = Params(r, r->params.FrameIndex);
             const bool sampled = d->profiling && (d->run_tick++ % d->profile_period) == 0;
-            const bool sort = (r->order_tick++ % TILE_ORDER_PERIOD) == 0;
+            const bool sort = (r->order_tick++ % TILE_ORDER_PERIOD) == 0 && !Masked(r);
             for (uint32_t g = 0; g < K; g++) {
+                if (G[g].tile_count == 0) continue;   // a group without an active tile
                 event_pair ep{};
                 if (g == 0)
                     if (int e = BeginTimed(d, PT_KERNEL_EXTEND, ep, sampled)) return e;
@@ -1507,7 +1573,7 @@ static int RunRoundsSplit(pt_device* d, pt_basic_renderer* r, uint64_t k, uint32
                     if (int e = EndTimed(d, ep)) return e;
                 if (sort) PT_HIP(pt_launch_tile_order(r->slots, S[g], K, g));
             }
-            r->rays += r->valid_slots;
+            r->rays += RoundSlots(r);
         }
         return 0;
     };
@@ -1530,13 +1596,20 @@ static int RunRoundsSplit(pt_device* d, pt_basic_renderer* r, uint64_t k, uint32
 static int RunRounds(pt_device* d, pt_basic_renderer* r, uint64_t k)
 {
     if (!r || CheckReady(r) != 0) return -1;
+    if (Masked(r) && r->active_tiles == 0) {   // nothing to launch: the rounds still take their seeds
+        r->params.FrameIndex += k;
+        return 0;
+    }
     uint32_t B = r->round_batch;
-    if (B == 0) B = RoundFused(r, r->slots) && r->fused == 1 ? AUTO_BATCH : 1u;
+    if (B == 0) B = RoundFused(r, ActiveSlots(r)) && r->fused == 1 ? AUTO_BATCH : 1u;
     if (B > 1) {
         PT_HIP(hipSetDevice(d->id));
         if (int e = EnsureSpill(r)) return e;
         if (int e = SyncRecordForm(d, r)) return e;
         if (pt_rounds_available(r->slots)) {
+            if (Masked(r))
+                if (int e = EnsureOrderGroups(d, r, 1)) return e;
+            const ptd::dslots L = ActiveSlots(r);
             const ptd::dframe F = Frame(r);
             while (k > 0) {
                 const uint32_t n = (uint32_t)std::min<uint64_t>(k, B);
@@ -1551,12 +1624,13 @@ static int RunRounds(pt_device* d, pt_basic_renderer* r, uint64_t k)
                 d->run_tick += n;
                 event_pair ep{};
                 if (int e = BeginTimed(d, PT_KERNEL_ROUNDS, ep, sampled, n)) return e;
-                PT_HIP(pt_launch_rounds(r->scene->d, r->slots, F, P, ShadeMats(r), d->stream));
+                PT_HIP(pt_launch_rounds(r->scene->d, L, F, P, ShadeMats(r), d->stream));
                 if (int e = EndTimed(d, ep)) return e;
-                // The batch's block times order the next batch.
-                for (uint32_t g = 0; g < r->order_groups; g++)
+                // The batch's block times order the next batch (natural
+                // order under a mask).
+                for (uint32_t g = 0; !Masked(r) && g < r->order_groups; g++)
                     PT_HIP(pt_launch_tile_order(r->slots, d->stream, r->order_groups, g));
-                r->rays += r->valid_slots * n;
+                r->rays += RoundSlots(r) * n;
                 k -= n;
             }
             return 0;
@@ -1613,6 +1687,57 @@ int ptGetBasicRendererSplit(const pt_basic_renderer* r, uint32_t* groups, uint32
     const uint32_t K = SplitGroups(r);
     if (groups) *groups = K;
     if (timed_tiles) *timed_tiles = pt_tile_group_count(r->slots.tile_count, K, 0);
+    if (tiles) *tiles = r->slots.tile_count;
+    return 0;
+}
+
+// Active tile set.  Setting or clearing it waits for the device and rewrites
+// the order array for the current group structure (WriteOrder).
+int ptSetBasicRendererActiveTiles(pt_device* d, pt_basic_renderer* r, const uint8_t* mask, uint32_t tiles)
+{
+    if (!d || !r) { SetError("ptSetBasicRendererActiveTiles: null argument"); return -1; }
+    if (r->dev != d) { SetError("ptSetBasicRendererActiveTiles: renderer of another device"); return -1; }
+    if (r->nranks != 1 || r->streams != 1) {
+        SetError("ptSetBasicRendererActiveTiles: partitioned and multi-stream renderers take no active tile set");
+        return -1;
+    }
+    if (!mask && tiles != 0) { SetError("ptSetBasicRendererActiveTiles: null mask with %u tiles", tiles); return -1; }
+    if (mask && tiles != r->slots.tile_count) {
+        SetError("ptSetBasicRendererActiveTiles: %u tiles given, the renderer has %u", tiles, r->slots.tile_count);
+        return -1;
+    }
+    if (!mask && !Masked(r)) return 0;
+    PT_HIP(hipSetDevice(d->id));
+    std::vector<uint8_t> previous;
+    const uint32_t previous_tiles = r->active_tiles;
+    const uint64_t previous_slots = r->active_slots;
+    previous.swap(r->mask);
+    r->active_tiles = 0;
+    r->active_slots = 0;
+    if (mask && tiles) {
+        r->mask.assign(mask, mask + tiles);
+        const uint32_t w = r->buffer->width, h = r->buffer->height;
+        for (uint32_t t = 0; t < tiles; t++) {
+            if (!mask[t]) continue;
+            const uint32_t ty = t / r->tiles_x, tx = t - ty * r->tiles_x;
+            r->active_tiles++;
+            r->active_slots += (uint64_t)std::min(16u, w - tx * 16u) * std::min(16u, h - ty * 16u);
+        }
+    }
+    if (int e = WriteOrder(d, r, r->order_groups)) {
+        // The order array is as it was: so is the set.
+        r->mask.swap(previous);
+        r->active_tiles = previous_tiles;
+        r->active_slots = previous_slots;
+        return e;
+    }
+    return 0;
+}
+
+int ptGetBasicRendererActiveTiles(const pt_basic_renderer* r, uint32_t* active, uint32_t* tiles)
+{
+    if (!r) { SetError("ptGetBasicRendererActiveTiles: null renderer"); return -1; }
+    if (active) *active = Masked(r) ? r->active_tiles : r->slots.tile_count;
     if (tiles) *tiles = r->slots.tile_count;
     return 0;
 }
@@ -1728,6 +1853,7 @@ int ptRenderFrame(pt_device* d, pt_basic_renderer* r, uint64_t target_samples, u
 {
     if (!d || !r) { SetError("null argument"); return -1; }
     if (max_rounds < 2) { SetError("ptRenderFrame: max_rounds must be >= 2"); return -1; }
+    if (Masked(r)) { SetError("ptRenderFrame: an active tile set is in place (ptSetBasicRendererActiveTiles)"); return -1; }
     if (int e = ptResetBasicRenderer(d, r)) return e;
     if (int e = ptRunBasicRenderer(d, r, 2)) return e;
     uint32_t rounds = 2;
@@ -2376,6 +2502,42 @@ int ptComputeFrameStatistics(pt_device* d, pt_sample_buffer* a, pt_sample_buffer
     s.min_luminance = pt_f2u(s.max_luminance) ? pt_u2f(~pt_f2u(s.min_luminance)) : 0.0f;
     s.min_samples = pt_f2u(s.max_samples) ? pt_u2f(~pt_f2u(s.min_samples)) : 0.0f;
     *out = s;
+    return 0;
+}
+
+// Per-tile statistics (stats.hip): one launch, one
+// read-back of tiles x 32 bytes.
+int ptComputeTileStatistics(pt_device* d, pt_sample_buffer* a, pt_sample_buffer* b, float noise_threshold,
+                            pt_tile_statistics* out)
+{
+    if (!d || !a || !out) { SetError("null argument"); return -1; }
+    if (b == a) { SetError("tile statistics: a and b are the same sample buffer"); return -1; }
+    if (a->dev != d || (b && b->dev != d)) { SetError("tile statistics: sample buffer of another device"); return -1; }
+    if (b && (b->width != a->width || b->height != a->height)) {
+        SetError("tile statistics: size mismatch (a %ux%u, b %ux%u)", a->width, a->height, b->width, b->height);
+        return -1;
+    }
+    if (!pt_tile_stats_threshold_ok(noise_threshold)) {
+        SetError("tile statistics: the noise threshold is NaN or negative");
+        return -1;
+    }
+    const size_t tiles = (size_t)((a->width + PT_TILE_SIZE - 1) / PT_TILE_SIZE) * ((a->height + PT_TILE_SIZE - 1) / PT_TILE_SIZE);
+    if (tiles == 0) return 0;
+    PT_HIP(hipSetDevice(d->id));
+    if (tiles > d->tile_stats.count) {
+        // The old records may still be read by a queued copy.
+        if (d->tile_stats.ptr) PT_WAIT(d);
+        if (hipError_t e = d->tile_stats.alloc(tiles); e != hipSuccess) {
+            SetError("tile statistics allocation failed: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+    }
+    PT_TIMED(d, PT_KERNEL_STATS,
+             pt_launch_tile_statistics(a->accum, b ? b->accum : nullptr, a->width, a->height, noise_threshold,
+                                       d->tile_stats.ptr, d->stream));
+    PT_HIP(hipMemcpyAsync(out, d->tile_stats.ptr, tiles * sizeof(pt_tile_statistics), hipMemcpyDeviceToHost,
+                          d->stream));
+    PT_WAIT(d);
     return 0;
 }
 

@@ -1,8 +1,9 @@
 // stats.hip — frame statistics of one accumulator or of a pair (no reference
-// counterpart), and the sample-buffer add that combines
-// two halves on the device.
+// counterpart), the same classes and pair rule counted per
+// 16 x 16 tile (row 10; tile_statistics_kernel below), and the sample-buffer
+// add that combines two halves on the device.
 //
-// Statistics: one pass, 16 B per pixel and accumulator, float4 loads.  The
+// Frame statistics: one pass, 16 B per pixel and accumulator, float4 loads.  The
 // classes, the bins and the pair rule are include/pt_stats.h's, shared with
 // the host implementation (csrc/scene/stats.cpp).  Everything written is an
 // integer count or a min/max of float bit patterns, so the order in which
@@ -187,6 +188,69 @@ __global__ __launch_bounds__(STATS_BLOCK) void frame_statistics_kernel(const flo
     }
 }
 
+// Per-tile statistics: one 256-thread block per 16 x 16
+// tile, one pixel per thread (thread t: column t & 15, row t >> 4, so a wave
+// reads four 256-byte row pieces).  The pixel rule is pt_stats.h's
+// pt_tile_stats_pixel, the host's.  No atomics: each count is the popcount of
+// a wave ballot, min and max of the .w bits are wave reductions (the minimum
+// as the maximum of the complement, 0 = no filled lane), the four waves'
+// partial results meet in LDS and thread 0 writes the 32-byte record with two
+// 16-byte stores.  Threads outside the image load nothing and count nowhere.
+constexpr uint32_t TILE_STATS_WAVES = 4;
+enum { T_FILLED, T_EMPTY, T_NONFINITE, T_PAIR, T_OVER, T_MIN_W, T_MAX_W, T_COUNT };
+
+template <bool PAIR>
+__global__ __launch_bounds__(256) void tile_statistics_kernel(const float4* __restrict__ A,
+                                                              const float4* __restrict__ B, uint32_t width,
+                                                              uint32_t height, uint32_t tiles_x, float threshold,
+                                                              pt_tile_statistics* __restrict__ out)
+{
+    __shared__ uint32_t part[TILE_STATS_WAVES][T_COUNT];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6;
+    const uint32_t tile = blockIdx.x, ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const uint32_t x = tx * PT_TILE_SIZE + (tid & 15u), y = ty * PT_TILE_SIZE + (tid >> 4);
+    uint32_t flags = 0, wb = 0;
+    if (x < width && y < height) {
+        const size_t i = (size_t)y * width + x;
+        const float4 a4 = A[i];
+        const float4 b4 = PAIR ? B[i] : make_float4(0, 0, 0, 0);
+        const float a[4] = {a4.x, a4.y, a4.z, a4.w}, b[4] = {b4.x, b4.y, b4.z, b4.w};
+        flags = pt_tile_stats_pixel(a, b, PAIR, threshold, &wb);
+    }
+    const bool filled = (flags & PT_TILE_PX_FILLED) != 0;
+    const uint32_t n_filled = (uint32_t)__popcll(__ballot(filled));
+    const uint32_t n_empty = (uint32_t)__popcll(__ballot((flags & PT_TILE_PX_EMPTY) != 0));
+    const uint32_t n_nonfinite = (uint32_t)__popcll(__ballot((flags & PT_TILE_PX_NONFINITE) != 0));
+    const uint32_t n_pair = PAIR ? (uint32_t)__popcll(__ballot((flags & PT_TILE_PX_PAIR) != 0)) : 0u;
+    const uint32_t n_over = PAIR ? (uint32_t)__popcll(__ballot((flags & PT_TILE_PX_OVER) != 0)) : 0u;
+    const uint32_t min_w = WaveMax(filled ? ~wb : 0u), max_w = WaveMax(filled ? wb : 0u);
+    if ((tid & 63u) == 0) {
+        part[wave][T_FILLED] = n_filled;
+        part[wave][T_EMPTY] = n_empty;
+        part[wave][T_NONFINITE] = n_nonfinite;
+        part[wave][T_PAIR] = n_pair;
+        part[wave][T_OVER] = n_over;
+        part[wave][T_MIN_W] = min_w;
+        part[wave][T_MAX_W] = max_w;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t v[T_COUNT];
+        for (uint32_t k = 0; k < T_COUNT; k++) v[k] = part[0][k];
+        for (uint32_t w = 1; w < TILE_STATS_WAVES; w++) {
+            for (uint32_t k = 0; k < T_MIN_W; k++) v[k] += part[w][k];
+            v[T_MIN_W] = v[T_MIN_W] > part[w][T_MIN_W] ? v[T_MIN_W] : part[w][T_MIN_W];
+            v[T_MAX_W] = v[T_MAX_W] > part[w][T_MAX_W] ? v[T_MAX_W] : part[w][T_MAX_W];
+        }
+        // filled > 0: the complement of the largest complement is the smallest
+        // .w; no filled pixel: both stay 0 (0.0f).
+        const uint32_t lo = v[T_FILLED] ? ~v[T_MIN_W] : 0u, hi = v[T_FILLED] ? v[T_MAX_W] : 0u;
+        uint4* rec = reinterpret_cast<uint4*>(out + tile);
+        rec[0] = make_uint4(v[T_FILLED], v[T_EMPTY], v[T_NONFINITE], v[T_PAIR]);
+        rec[1] = make_uint4(v[T_OVER], lo, hi, 0u);
+    }
+}
+
 // dst += src, each component in binary32 (numpy's a + b).
 __global__ __launch_bounds__(256) void accumulate_kernel(float4* __restrict__ dst, const float4* __restrict__ src,
                                                          uint64_t n)
@@ -218,6 +282,19 @@ hipError_t pt_launch_frame_statistics(const float4* a, const float4* b, uint64_t
         if (uniform) hipLaunchKernelGGL((ptd::frame_statistics_kernel<false, true>), grid, block, 0, st, a, b, n, out);
         else hipLaunchKernelGGL((ptd::frame_statistics_kernel<false, false>), grid, block, 0, st, a, b, n, out);
     }
+    return hipGetLastError();
+}
+
+hipError_t pt_launch_tile_statistics(const float4* a, const float4* b, uint32_t width, uint32_t height,
+                                     float threshold, pt_tile_statistics* out, hipStream_t st)
+{
+    const uint32_t tiles_x = (width + PT_TILE_SIZE - 1) / PT_TILE_SIZE, tiles_y = (height + PT_TILE_SIZE - 1) / PT_TILE_SIZE;
+    const uint64_t tiles = (uint64_t)tiles_x * tiles_y;
+    if (tiles == 0) return hipSuccess;
+    if (tiles > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)tiles), block(256);
+    if (b) hipLaunchKernelGGL(ptd::tile_statistics_kernel<true>, grid, block, 0, st, a, b, width, height, tiles_x, threshold, out);
+    else hipLaunchKernelGGL(ptd::tile_statistics_kernel<false>, grid, block, 0, st, a, b, width, height, tiles_x, threshold, out);
     return hipGetLastError();
 }
 

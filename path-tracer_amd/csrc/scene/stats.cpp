@@ -66,6 +66,44 @@ extern "C" int ptsFrameStatistics(uint32_t width, uint32_t height, const float* 
     return 0;
 }
 
+// Per-tile statistics: the pixel rule is pt_stats.h's
+// pt_tile_stats_pixel, shared with the device kernel.
+extern "C" int ptsTileStatistics(uint32_t width, uint32_t height, const float* accum_a, const float* accum_b,
+                                 float noise_threshold, pt_tile_statistics* out)
+{
+    if (!accum_a || !out || width == 0 || height == 0 || accum_a == accum_b) return -1;
+    if (!pt_tile_stats_threshold_ok(noise_threshold)) return -1;
+    const uint32_t tiles_x = (width + PT_TILE_SIZE - 1) / PT_TILE_SIZE, tiles_y = (height + PT_TILE_SIZE - 1) / PT_TILE_SIZE;
+    for (uint32_t ty = 0; ty < tiles_y; ty++) {
+        for (uint32_t tx = 0; tx < tiles_x; tx++) {
+            pt_tile_statistics s;
+            std::memset(&s, 0, sizeof(s));
+            uint32_t min_w = 0xFFFFFFFFu, max_w = 0;
+            const uint32_t x1 = pt_umin(width, (tx + 1) * PT_TILE_SIZE), y1 = pt_umin(height, (ty + 1) * PT_TILE_SIZE);
+            for (uint32_t y = ty * PT_TILE_SIZE; y < y1; y++) {
+                for (uint32_t x = tx * PT_TILE_SIZE; x < x1; x++) {
+                    const size_t i = ((size_t)y * width + x) * 4;
+                    uint32_t wb = 0;
+                    const uint32_t f = pt_tile_stats_pixel(accum_a + i, accum_b ? accum_b + i : accum_a + i,
+                                                           accum_b != nullptr, noise_threshold, &wb);
+                    s.filled += (f & PT_TILE_PX_FILLED) != 0;
+                    s.empty += (f & PT_TILE_PX_EMPTY) != 0;
+                    s.nonfinite += (f & PT_TILE_PX_NONFINITE) != 0;
+                    s.pair += (f & PT_TILE_PX_PAIR) != 0;
+                    s.over += (f & PT_TILE_PX_OVER) != 0;
+                    if (f & PT_TILE_PX_FILLED) {
+                        min_w = pt_umin(min_w, wb);
+                        max_w = max_w > wb ? max_w : wb;
+                    }
+                }
+            }
+            if (s.filled) { s.min_count = pt_u2f(min_w); s.max_count = pt_u2f(max_w); }
+            out[(size_t)ty * tiles_x + tx] = s;
+        }
+    }
+    return 0;
+}
+
 extern "C" int ptsStatsBin(float v) { return pt_stats_bin(v); }
 extern "C" double ptsStatsBinEdge(int bin) { return bin < 0 || bin > PT_STATS_BINS ? 0.0 : pt_stats_bin_edge(bin); }
 extern "C" int ptsStatsPercentileBin(const uint32_t* histogram, double q)

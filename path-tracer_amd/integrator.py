@@ -293,6 +293,112 @@ def frame_statistics_host(accum: np.ndarray, other: "np.ndarray | None" = None) 
     return FrameStatistics(out)
 
 
+def _tile_grid(width: int, height: int):
+    """(tiles_y, tiles_x) of a width x height frame's 16 x 16 tiles."""
+    return (int(height) + N.TILE_SIZE - 1) // N.TILE_SIZE, (int(width) + N.TILE_SIZE - 1) // N.TILE_SIZE
+
+
+def tile_statistics_host(accum: np.ndarray, other: "np.ndarray | None" = None, threshold: float = 0.1) -> np.ndarray:
+    """Per-tile statistics on the CPU (ptsTileStatistics, libptscene.so), which
+    SampleBuffer.tile_statistics equals bit for bit: a (tiles_y, tiles_x) array
+    of TILE_STATS_DTYPE records, one per 16 x 16 tile (clipped at the right and
+    bottom edges).  accum, other: (H, W, 4) accumulators as for
+    frame_statistics_host; without `other`, pair and over are 0.  over counts
+    the pair pixels whose relative half-difference exceeds `threshold`."""
+    a = _accumulator(accum)
+    b = None
+    if other is not None:
+        b = _accumulator(other, "second accumulator")
+        if b.shape != a.shape:
+            raise ValueError(f"accumulators of shapes {a.shape} and {b.shape}")
+    out = np.zeros(_tile_grid(a.shape[1], a.shape[0]), dtype=N.TILE_STATS_DTYPE)
+    rc = N.scene_lib().ptsTileStatistics(a.shape[1], a.shape[0], N.fptr(a), N.fptr(b) if b is not None else None,
+                                         float(threshold), out.ctypes.data)
+    if rc != 0:
+        raise PathTracerError(f"ptsTileStatistics: bad arguments (status {rc})")
+    return out
+
+
+def tile_mask_of_region(width: int, height: int, x0: int, y0: int, x1: int, y1: int) -> np.ndarray:
+    """The (tiles_y, tiles_x) uint8 mask of the 16 x 16 tiles of a width x
+    height frame that hold a pixel of [x0, x1) x [y0, y1) (clipped to the
+    frame): the argument of BasicRenderer.set_active_tiles that re-renders
+    that region."""
+    ty, tx = _tile_grid(width, height)
+    mask = np.zeros((ty, tx), dtype=np.uint8)
+    x0, y0, x1, y1 = max(int(x0), 0), max(int(y0), 0), min(int(x1), int(width)), min(int(y1), int(height))
+    if x0 < x1 and y0 < y1:
+        mask[y0 // N.TILE_SIZE:(y1 - 1) // N.TILE_SIZE + 1, x0 // N.TILE_SIZE:(x1 - 1) // N.TILE_SIZE + 1] = 1
+    return mask
+
+
+# refine_tiles' floor on the rounds of a tile (tools/exp_active_tiles.py;
+# DESIGN.md §6 row 10).
+REFINE_MIN_ROUNDS = 128
+
+
+def refine_tiles(renderer_a: "BasicRenderer", renderer_b: "BasicRenderer", threshold: float, q: float = 0.95,
+                 min_rounds: int = REFINE_MIN_ROUNDS, rounds_per_step: int = 8, max_rounds: int = 1024,
+                 min_count: "float | None" = None):
+    """Go on rendering a frame's two halves on the tiles that still need it.
+    renderer_a and renderer_b are full-frame renderers on one device, on
+    sample buffers of one size, FrameIndex apart by 1 << 24, already Reset
+    (and, after a camera move, with FrameHistory.begin_frame's history in
+    place); rounds continue from their current state.  In steps of
+    `rounds_per_step` rounds (run_rounds on both, under one active tile set)
+    the per-tile pair statistics of the two sample buffers are computed in one
+    device pass, and a tile stays active while
+      - it has run fewer than `min_rounds` rounds here, or
+      - no pixel of it is a pair pixel yet (pair == 0), or
+      - over > (1 - q) * pair: more than a share 1 - q of its pair pixels have
+        a relative half-difference above `threshold`, or
+      - `min_count` is given and some filled pixel of a + b has fewer samples
+        (the tile's min_count; disoccluded pixels after a reprojection).
+    It ends when no tile is active or after `max_rounds` rounds.  Returns
+    (rounds, stats): the rounds run here per tile, (tiles_y, tiles_x) int64,
+    and the last tile statistics.  The renderers' active tile sets are
+    cleared on return, on an error too.
+
+    min_rounds is a floor against a bias, not a tuning knob: a tile frozen
+    after n rounds holds only the paths that completed within n rounds, the
+    short ones, so it is darker than the converged tile wherever long paths
+    carry light -- the bias of cutting a whole frame early, here local to
+    the frozen tiles, where neighbours that ran longer make it visible.  The
+    default is the value chosen in DESIGN.md §6 row 10."""
+    if rounds_per_step < 1 or min_rounds < 0 or max_rounds < 1:
+        raise ValueError("rounds_per_step >= 1, min_rounds >= 0 and max_rounds >= 1 are required")
+    if not 0.0 < q <= 1.0:
+        raise ValueError("q must lie in (0, 1]")
+    sa, sb = renderer_a.sample_buffer, renderer_b.sample_buffer
+    if (sa.width, sa.height) != (sb.width, sb.height):
+        raise ValueError("the two renderers' sample buffers differ in size")
+    active = np.ones(_tile_grid(sa.width, sa.height), dtype=bool)
+    rounds = np.zeros(active.shape, dtype=np.int64)
+    done, stats = 0, None
+    try:
+        while True:
+            step = min(rounds_per_step, max_rounds - done)
+            if done < min_rounds:
+                step = min(step, min_rounds - done)   # every tile stops at min_rounds exactly, if it stops there
+            for r in (renderer_a, renderer_b):
+                r.set_active_tiles(None if active.all() else active)
+                r.run_rounds(step)
+            done += step
+            rounds[active] += step
+            stats = sa.tile_statistics(sb, threshold)
+            need = (stats["pair"] == 0) | (stats["over"] > (1.0 - q) * stats["pair"])
+            if min_count is not None:
+                need |= (stats["filled"] > 0) & (stats["min_count"] < np.float32(min_count))
+            if done < min_rounds:
+                need[:] = True
+            active &= need
+            if not active.any() or done >= max_rounds:
+                return rounds, stats
+    finally:
+        for r in (renderer_a, renderer_b):
+            r.set_active_tiles(None)
+
+
 def render_until_noise(renderer_a: "BasicRenderer", renderer_b: "BasicRenderer", threshold: float, q: float = 0.95,
                        check_every: int = 8, min_pair_fraction: float = 0.99, max_rounds: int = 1024):
     """Render one frame as two independent halves until it is converged:
@@ -655,6 +761,18 @@ class SampleBuffer:
                "ptComputeFrameStatistics")
         return FrameStatistics(out)
 
+    def tile_statistics(self, other: "SampleBuffer | None" = None, threshold: float = 0.1) -> np.ndarray:
+        """Per-tile statistics on the device (ptComputeTileStatistics; blocks,
+        one launch): a (tiles_y, tiles_x) array of TILE_STATS_DTYPE records of
+        this buffer's 16 x 16 tiles, or, with `other`, of this + other with
+        the pair counts (over: pair pixels whose relative half-difference
+        exceeds `threshold`).  Neither buffer is written."""
+        out = np.zeros(_tile_grid(self.width, self.height), dtype=N.TILE_STATS_DTYPE)
+        _check(N.hip_lib().ptComputeTileStatistics(self.device.handle, self._h,
+                                                   other.handle if other is not None else None, float(threshold),
+                                                   out.ctypes.data), "ptComputeTileStatistics")
+        return out
+
     def accumulate(self, src: "SampleBuffer"):
         """This accumulator += src's, per component in float32, on the device
         (ptAccumulateSampleBuffer; enqueues).  src is not written."""
@@ -821,6 +939,33 @@ class BasicRenderer:
         u = C.c_uint32(0)
         _check(N.hip_lib().ptGetBasicRendererClassLists(self._h, C.byref(u)), "ptGetBasicRendererClassLists")
         return bool(u.value)
+
+    def set_active_tiles(self, mask: "np.ndarray | None"):
+        """The tiles the following rounds run on (ptSetBasicRendererActiveTiles):
+        a (tiles_y, tiles_x) array, non-zero = active (tile_mask_of_region
+        builds one), or None for every tile.  An active tile's results equal
+        an unmasked render's bit for bit; an inactive tile is not touched.
+        Full-frame, single-stream renderers only; render_frame is refused
+        while a mask is set.  Waits for the device."""
+        if mask is None:
+            _check(N.hip_lib().ptSetBasicRendererActiveTiles(self.device.handle, self._h, None, 0),
+                   "ptSetBasicRendererActiveTiles")
+            return
+        m = np.asarray(mask)
+        grid = _tile_grid(self.sample_buffer.width, self.sample_buffer.height)
+        if m.shape != grid:
+            raise ValueError(f"mask of shape {m.shape}, the frame has {grid} tiles")
+        m = np.ascontiguousarray(m != 0, dtype=np.uint8)
+        _check(N.hip_lib().ptSetBasicRendererActiveTiles(self.device.handle, self._h, m.ctypes.data, m.size),
+               "ptSetBasicRendererActiveTiles")
+
+    def active_tiles(self) -> dict:
+        """{active, tiles}: the tiles the next round launches and all tiles
+        (ptGetBasicRendererActiveTiles)."""
+        a, t = C.c_uint32(0), C.c_uint32(0)
+        _check(N.hip_lib().ptGetBasicRendererActiveTiles(self._h, C.byref(a), C.byref(t)),
+               "ptGetBasicRendererActiveTiles")
+        return {"active": int(a.value), "tiles": int(t.value)}
 
     def run_rounds(self, count: int):
         """count consecutive Run(1) calls (one new FrameIndex each), batched

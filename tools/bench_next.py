@@ -32,11 +32,19 @@
   one in which every shape is flagged as moved (identity matrices, so the
   same taps), beside ptReprojectSampleBuffer's kernel, ptRenderSampleBuffer
   and one a-trous iteration in the same run; every figure three times.
+* tiles (ptComputeTileStatistics, stats.hip, and ptSetBasicRendererActiveTiles;
+  DESIGN.md §6 row 10): kernel ms of the per-tile statistics launch, single
+  and pair, beside ptComputeFrameStatistics on the same buffers in the same
+  run, at 1920x1080 and 3840x2160; and ms per round of C3 at 1920x1080 with
+  100, 50, 25 and 6 % of the tiles active, as one contiguous region and
+  spread as a lattice: the extend + shade kernel times of single-stream
+  rounds (HIP events) and the wall time per round of batches in the automatic
+  schedule; every figure three times.
 * host builds (§8(f) row 3): mesh BVH build of a 1.96 M-face mesh on 1 and
   on all of the job's threads, and the RGB -> spectrum table.
 
 Kernel times are HIP events on the device stream (ptGetKernelStats).
-Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|reproject|reproject_moving|preview|openpbr|host ...]
+Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|preview|openpbr|host ...]
 (default: all).
 """
 import json
@@ -210,6 +218,115 @@ def stats(pt, dev):
         for x in halves + flat:
             x.close()
     ds.close()
+    return out
+
+
+def tile_masks(tiles_x, tiles_y):
+    """{name: (tiles_y, tiles_x) uint8}: about 100, 50, 25 and 6 % of the
+    tiles, as a centred rectangle (region_*) and as a lattice (spread_*:
+    checkerboard, every second tile of every second row, every fourth of
+    every fourth)."""
+    ty, tx = np.mgrid[0:tiles_y, 0:tiles_x]
+    masks = {"all": np.ones((tiles_y, tiles_x), np.uint8)}
+    for pct, share in ((50, 0.5), (25, 0.25), (6, 0.0625)):
+        w, h = int(round(tiles_x * share ** 0.5)), int(round(tiles_y * share ** 0.5))
+        x0, y0 = (tiles_x - w) // 2, (tiles_y - h) // 2
+        masks[f"region_{pct}"] = ((tx >= x0) & (tx < x0 + w) & (ty >= y0) & (ty < y0 + h)).astype(np.uint8)
+    masks["spread_50"] = ((tx + ty) % 2 == 0).astype(np.uint8)
+    masks["spread_25"] = ((tx % 2 == 0) & (ty % 2 == 0)).astype(np.uint8)
+    masks["spread_6"] = ((tx % 4 == 0) & (ty % 4 == 0)).astype(np.uint8)
+    return masks
+
+
+def tiles(pt, dev):
+    """statistics: per size, tile_{single|pair}_ms and frame_{single|pair}_ms,
+    the per-tile launch and ptComputeFrameStatistics' on the same rendered
+    halves (C3, 8 rounds each), and their ratio.  masked_rounds (C3,
+    1920x1080): per mask its active share, kernel_ms = extend + shade kernel
+    time per round of single-stream rounds (split off, HIP events), and
+    wall_ms = wall time per round of run_rounds(32) + synchronize in the
+    automatic schedule (tile groups when at least 2 048 tiles are active).
+    Each time is a list: the mean of 10 timed calls (batches) after a warm-up
+    one, taken three times in turn."""
+    out = {"statistics": {}, "masked_rounds": {}}
+    scene = pt.Scene.config(3)
+    ds = pt.DeviceScene(dev)
+    ds.update(scene)
+    for W, H in ((1920, 1080), (3840, 2160)):
+        halves = [pt.SampleBuffer(dev, W, H), pt.SampleBuffer(dev, W, H)]
+        for sb, frame in zip(halves, (0, 1 << 24)):
+            r = pt.BasicRenderer(dev, ds, sb)
+            r.RenderFlags = 3
+            r.FrameIndex = frame
+            r.reset()
+            r.run(8)
+            dev.synchronize()
+            r.close()
+        a, b = halves
+        runs = {"frame_single_ms": lambda: a.statistics(), "frame_pair_ms": lambda: a.statistics(b),
+                "tile_single_ms": lambda: a.tile_statistics(), "tile_pair_ms": lambda: a.tile_statistics(b, 0.1)}
+        res = {"pixels": W * H, "tiles": ((W + 15) // 16) * ((H + 15) // 16)}
+        for key in runs:
+            res[key] = []
+        for _ in range(3):
+            for key, fn in runs.items():
+                fn()   # warm
+                ms, _ = timed(dev, K_STATS, fn, 10)
+                res[key].append(round(ms, 4))
+        for kind, bytes_px in (("single", 16.0), ("pair", 32.0)):
+            res[f"tile_over_frame_{kind}"] = [round(t / f, 3) for t, f in zip(res[f"tile_{kind}_ms"], res[f"frame_{kind}_ms"])]
+            res[f"tile_{kind}_gbps"] = [round(bytes_px * W * H / (t * 1e-3) / 1e9, 1) for t in res[f"tile_{kind}_ms"]]
+        out["statistics"][f"{W}x{H}"] = res
+        for x in halves:
+            x.close()
+
+    W, H = 1920, 1080
+    sb = pt.SampleBuffer(dev, W, H)
+    r = pt.BasicRenderer(dev, ds, sb)
+    r.RenderFlags = 3
+    r.reset()
+    r.run(2)
+    r.run_rounds(16)
+    masks = tile_masks((W + 15) // 16, (H + 15) // 16)
+    masks = {"none": None, **masks}
+    res = {name: {"active_share": 1.0 if m is None else round(float(m.mean()), 4), "kernel_ms": [], "wall_ms": [],
+                  "groups": None} for name, m in masks.items()}
+
+    def kernel_ms():
+        dev.synchronize()
+        dev.reset_kernel_stats()
+        dev.set_profiling(True, period=1)
+        r.run_rounds(10)
+        dev.synchronize()
+        (ne, me), (ns, ms) = dev.kernel_stats(K_EXTEND), dev.kernel_stats(K_SHADE)
+        dev.set_profiling(False)
+        return me / max(ne, 1) + ms / max(ns, 1)
+
+    def wall_ms():
+        dev.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(10):
+            r.run_rounds(32)
+        dev.synchronize()
+        return (time.perf_counter() - t0) / 320 * 1e3
+
+    for _ in range(3):
+        for name, m in masks.items():
+            r.set_active_tiles(m)
+            r.set_fused_rounds(0)
+            r.set_split(1)
+            r.run_rounds(10)   # warm
+            res[name]["kernel_ms"].append(round(kernel_ms(), 4))
+            r.set_fused_rounds(1)
+            r.set_split(0)
+            res[name]["groups"] = r.split()["groups"]
+            r.run_rounds(32)   # warm
+            res[name]["wall_ms"].append(round(wall_ms(), 4))
+    r.set_active_tiles(None)
+    out["masked_rounds"] = res
+    for x in (r, sb, ds):
+        x.close()
+    scene.close()
     return out
 
 
@@ -412,7 +529,7 @@ def host_builds(pt):
 
 def main():
     pt = load()
-    entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "reproject": reproject, "reproject_moving": reproject_moving,
+    entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "tiles": tiles, "reproject": reproject, "reproject_moving": reproject_moving,
                "preview": preview, "openpbr": openpbr}
     want = sys.argv[1:] or list(entries) + ["host"]
     dev = pt.Device(0)

@@ -38,6 +38,7 @@ run asan_scenes "$A" scene $(ls -d "$C"/scenes/s*/ | sed 's|$|scene.json|') "$C/
 run asan_render "$A" render
 run asan_denoise "$A" denoise
 run asan_stats "$A" stats
+run asan_tile_stats "$A" tile_stats
 run asan_reproject "$A" reproject
 run asan_reproject_moving "$A" reproject_moving
 PT_BVH_THREADS=8 run tsan_bvh "$T" bvh 300000

@@ -21,6 +21,10 @@
 //                               small random, empty and NaN / inf / denormal
 //                               images, single and pair, one pixel included;
 //                               rejected arguments
+//   san_driver tile_stats       ptsTileStatistics on random, empty and NaN / inf /
+//                               denormal images from 1x1 to 67x45, single and
+//                               pair, thresholds 0 to +inf, against
+//                               ptsFrameStatistics' totals; rejected arguments
 //   san_driver reproject_moving ptsShapeMotion and ptsReprojectMoving on random
 //                               tables with NaN and flagged records, 1x1 to 67x45
 //   san_driver reproject        ptsReproject and ptsCentralCameraRay on random
@@ -284,6 +288,74 @@ static int Stats()
     return bad != 0;
 }
 
+// ptsTileStatistics: the records lie in an array of
+// exactly tiles_x * tiles_y elements, so a write past the last tile is ASan's.
+static int TileStats()
+{
+    std::mt19937 rng(15);
+    std::uniform_real_distribution<float> u(0.0f, 4.0f);
+    const float nan = std::nanf(""), inf = HUGE_VALF;
+    const float odd[] = {0.0f, -0.0f, -1.0f, nan, inf, -inf, 1e-45f, 1e-38f, 3e38f, 1.0f, 4294967296.0f, 2.3283064e-10f};
+    const uint32_t sizes[][2] = {{1, 1}, {1, 7}, {3, 2}, {15, 15}, {16, 16}, {17, 16}, {16, 17}, {17, 33}, {33, 31},
+                                 {40, 24}, {67, 45}};
+    const float thresholds[] = {0.0f, 0.1f, 1.0f, inf};
+    int bad = 0;
+    for (auto& wh : sizes) {
+        const uint32_t W = wh[0], H = wh[1];
+        const size_t n = (size_t)W * H, tiles = (size_t)((W + 15) / 16) * ((H + 15) / 16);
+        // kind 0: random; 1: all empty; 2: every component drawn from the odd values (NaN, inf, denormals ...)
+        for (int kind = 0; kind < 3; kind++) {
+            std::vector<float> a(4 * n), b(4 * n);
+            for (std::vector<float>* v : {&a, &b}) {
+                for (size_t i = 0; i < 4 * n; i++) {
+                    if (kind == 0) (*v)[i] = i % 4 == 3 ? (float)(rng() % 5) : u(rng);
+                    else if (kind == 1) (*v)[i] = 0.0f;
+                    else (*v)[i] = odd[rng() % (sizeof(odd) / sizeof(odd[0]))];
+                }
+            }
+            for (int pair = 0; pair < 2; pair++) {
+                pt_frame_statistics f;
+                if (ptsFrameStatistics(W, H, a.data(), pair ? b.data() : nullptr, &f) != 0) { std::printf("tile_stats: failed\n"); return 1; }
+                uint64_t over_before = ~0ull;
+                for (float t : thresholds) {
+                    std::vector<pt_tile_statistics> s(tiles);
+                    if (ptsTileStatistics(W, H, a.data(), pair ? b.data() : nullptr, t, s.data()) != 0) { std::printf("tile_stats: failed\n"); return 1; }
+                    uint64_t filled = 0, empty = 0, nonfinite = 0, pairs = 0, over = 0;
+                    for (const pt_tile_statistics& r : s) {
+                        filled += r.filled; empty += r.empty; nonfinite += r.nonfinite; pairs += r.pair; over += r.over;
+                        bad += r.over > r.pair || r.reserved != 0 || r.filled + r.empty + r.nonfinite > 256;
+                        bad += r.filled ? !(r.min_count > 0.0f && r.min_count <= r.max_count) : (r.min_count != 0.0f || r.max_count != 0.0f);
+                    }
+                    bad += filled != f.filled || empty != f.empty || nonfinite != f.nonfinite || pairs != f.noise_pixels;
+                    bad += over > over_before || (t == inf && over != 0) || (!pair && pairs != 0);
+                    over_before = over;
+                    std::printf("tile_stats %ux%u kind %d pair %d threshold %g: %zu tiles, filled %llu empty %llu nonfinite %llu "
+                                "pair %llu over %llu\n", W, H, kind, pair, (double)t, tiles, (unsigned long long)filled,
+                                (unsigned long long)empty, (unsigned long long)nonfinite, (unsigned long long)pairs,
+                                (unsigned long long)over);
+                }
+            }
+        }
+    }
+    // rejected arguments leave `out` untouched
+    float acc[4] = {1, 1, 1, 1}, other[4] = {1, 2, 1, 1};
+    pt_tile_statistics out;
+    std::memset(&out, 0x55, sizeof(out));
+    const pt_tile_statistics before = out;
+    bad += ptsTileStatistics(1, 1, nullptr, nullptr, 0.1f, &out) == 0;
+    bad += ptsTileStatistics(1, 1, acc, nullptr, 0.1f, nullptr) == 0;
+    bad += ptsTileStatistics(0, 1, acc, nullptr, 0.1f, &out) == 0;
+    bad += ptsTileStatistics(1, 0, acc, nullptr, 0.1f, &out) == 0;
+    bad += ptsTileStatistics(1, 1, acc, acc, 0.1f, &out) == 0;
+    bad += ptsTileStatistics(1, 1, acc, other, nan, &out) == 0;
+    bad += ptsTileStatistics(1, 1, acc, other, -0.5f, &out) == 0;
+    bad += ptsTileStatistics(1, 1, acc, other, -inf, &out) == 0;
+    bad += std::memcmp(&out, &before, sizeof(out)) != 0;
+    bad += ptsTileStatistics(1, 1, acc, other, -0.0f, &out) != 0 || out.pair != 1 || out.over != 1;
+    std::printf("tile_stats: %d checks wrong\n", bad);
+    return bad != 0;
+}
+
 // A camera record at `pos`, turned by `yaw` about z from the configs' forward
 // direction (+y); To = T R, From = R^-1 T^-1, column-major.
 static pt_packed_camera SanCamera(uint32_t model, const float pos[3], float yaw)
@@ -503,7 +575,7 @@ static int ReprojectMoving()
 
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise|stats|reproject|reproject_moving ...\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise|stats|tile_stats|reproject|reproject_moving ...\n"); return 2; }
     std::string cmd = argv[1];
     if (cmd == "decode") return Decode(argc - 2, argv + 2);
     if (cmd == "model") return Model(argc - 2, argv + 2);
@@ -512,6 +584,7 @@ int main(int argc, char** argv)
     if (cmd == "bvh") return Bvh(argc > 2 ? (uint32_t)std::strtoul(argv[2], nullptr, 10) : 200000u);
     if (cmd == "denoise") return Denoise();
     if (cmd == "stats") return Stats();
+    if (cmd == "tile_stats") return TileStats();
     if (cmd == "reproject") return Reproject();
     if (cmd == "reproject_moving") return ReprojectMoving();
     std::fprintf(stderr, "unknown command %s\n", cmd.c_str());
