@@ -49,10 +49,17 @@ void SetError(const char* fmt, ...)
         }                                                                                    \
     } while (0)
 
+// A device array that owns its memory: freed when the buffer, or the object
+// it is a member of, goes away (with that object's device current and its
+// stream idle: the destroy functions see to both before their delete).
 template <class T>
 struct dbuf {
     T* ptr = nullptr;
     size_t count = 0;
+    dbuf() = default;
+    dbuf(const dbuf&) = delete;
+    dbuf& operator=(const dbuf&) = delete;
+    ~dbuf() { release(); }
     void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; count = 0; }
     hipError_t upload(const T* src, size_t n)
     {
@@ -109,7 +116,7 @@ struct pt_device {
     hipEvent_t join_event[PT_MAX_SPLIT - 1] = {};
     // ptComputeFrameStatistics' result on the device: allocated at the first
     // call, cleared on `stream` before every launch.
-    pt_frame_statistics* stats = nullptr;
+    dbuf<pt_frame_statistics> stats;
     uint32_t stats_variant = PT_STATS_VARIANT_AUTO;
     // ptComputeTileStatistics' records on the device: grown on demand, every
     // record rewritten by each launch.
@@ -168,7 +175,7 @@ struct pt_preview {
     dbuf<pt_preview_aov> aov;
     dbuf<uint32_t> spill;
     dbuf<float> observe;                 // ObserveUnderD65's per-sample constants (preview.hip)
-    uint32_t* query = nullptr;
+    dbuf<uint32_t> query;                // the picked shape's index (ptRetrievePreviewQueryResult)
     bool rendered = false;
 };
 
@@ -202,7 +209,7 @@ struct pt_basic_renderer {
     bool grey_blocked = false;          // some live path cannot take it (until the next Reset / state write)
     dbuf<uint32_t> grey_count;          // pt_launch_grey_check's result word
     dbuf<uint32_t> cq_counts, cq_list;  // class-pure shade lists (ClassLists)
-    uint32_t cq_parity = 0;
+    uint32_t cq_parity[PT_MAX_SPLIT + 1] = {};   // per counter region (NextClassLists)
     uint32_t class_lists = 0;           // ptSetBasicRendererClassLists: 0 automatic, 1 off
     dbuf<float> lam;                    // lambda0 per slot (Sample is 0 between rounds)
     dbuf<float2> uv;
@@ -498,13 +505,14 @@ ptd::dparams Params(pt_basic_renderer* r, uint32_t seed)
     return P;
 }
 
+bool Spills(const pt_basic_renderer* r) { return r->scene->stack_needed > pt_extend_stack_cap(); }
+
 // Traversal stack entries beyond the kernel's LDS capacity live in a global
 // buffer of (needed - capacity) rows x one column per ray.
 int EnsureSpill(pt_basic_renderer* r)
 {
-    uint32_t need = r->scene->stack_needed, cap = pt_extend_stack_cap();
-    if (need <= cap) { r->slots.spill = nullptr; return 0; }
-    size_t rows = need - cap;
+    if (!Spills(r)) { r->slots.spill = nullptr; return 0; }
+    size_t rows = r->scene->stack_needed - pt_extend_stack_cap();
     PT_HIP(r->spill.alloc(rows * (size_t)r->slots.n));
     r->slots.spill = r->spill.ptr;
     return 0;
@@ -572,9 +580,6 @@ void ptDestroyDevice(pt_device* d)
         if (d->join_event[g]) (void)hipEventDestroy(d->join_event[g]);
     }
     if (d->fork_event) (void)hipEventDestroy(d->fork_event);
-    if (d->stats) (void)hipFree(d->stats);
-    d->tile_stats.release();
-    d->motion.release();
     if (d->motion_host) (void)hipHostFree(d->motion_host);
     if (d->motion_copied) (void)hipEventDestroy(d->motion_copied);
     (void)hipStreamDestroy(d->stream);
@@ -601,8 +606,6 @@ void ptDestroyScene(pt_device* d, pt_scene* s)
 {
     if (!s) return;
     if (d) (void)hipSetDevice(d->id);
-    s->textures.release(); s->material.release(); s->shapes.release(); s->shape_nodes.release();
-    s->faces.release(); s->vertices.release(); s->vertex_attr.release(); s->vertex_v.release(); s->mesh_nodes.release(); s->cameras.release(); s->atlas.release();
     delete s;
 }
 
@@ -826,7 +829,6 @@ int ptUpdateScene(pt_device* d, pt_scene* s, const pt_scene_packs* p, uint32_t d
             // Upload row-major, then re-lay the texels in 4x2 blocks
             // (AtlasIndex, pt_device.hpp) on the device.
             dbuf<float> stage;
-            struct release_stage { dbuf<float>& b; ~release_stage() { b.release(); } } guard{stage};
             PT_HIP(stage.upload(p->atlas, atlas_floats));
             PT_HIP(s->atlas.alloc(atlas_floats));
             PT_HIP(pt_launch_atlas_tile(reinterpret_cast<const float4*>(stage.ptr), reinterpret_cast<float4*>(s->atlas.ptr),
@@ -962,8 +964,6 @@ void ptDestroySampleBuffer(pt_device* d, pt_sample_buffer* b)
     if (!b) return;
     if (d) (void)hipSetDevice(d->id);
     if (b->accum) (void)hipFree(b->accum);
-    b->display.release();
-    b->display8.release();
     delete b;
 }
 
@@ -1088,10 +1088,6 @@ pt_basic_renderer* ptCreateBasicRendererStreams(pt_device* d, pt_scene* s, pt_sa
     }
     if (!ok) {
         SetError("renderer slot allocation failed (%u slots)", ns);
-        r->ray.release(); r->hit.release(); r->thr.release(); r->prob.release(); r->prob1.release(); r->grey_count.release();
-        r->lam.release(); r->uv.release(); r->act.release();
-        r->pos.release(); r->slotof.release(); r->outcome.release(); r->tilecost.release(); r->order.release();
-        r->done.release(); r->accx.release();
         delete r;
         return nullptr;
     }
@@ -1151,15 +1147,6 @@ void ptDestroyBasicRenderer(pt_device* d, pt_basic_renderer* r)
 {
     if (!r) return;
     if (d) { (void)hipSetDevice(d->id); (void)DeviceWait(d); }
-    r->ray.release(); r->hit.release(); r->thr.release(); r->prob.release(); r->prob1.release(); r->grey_count.release();
-    r->cq_counts.release(); r->cq_list.release();
-    r->lam.release();
-    r->uv.release(); r->act.release(); r->pos.release(); r->slotof.release(); r->outcome.release();
-    r->tilecost.release(); r->order.release();
-    r->done.release();
-    r->spill.release();
-    r->guard.release();
-    r->accx.release();
     delete r;
 }
 
@@ -1321,105 +1308,6 @@ static int ClassListBuffers(pt_device* d, pt_basic_renderer* r, uint32_t K)
     return 0;
 }
 
-static bool ClassListRounds(const pt_basic_renderer* r);
-static int EnsureOrderGroups(pt_device* d, pt_basic_renderer* r, uint32_t K);
-
-// Class-pure shade of one single-stream round over every tile (the
-// renderer's rounds outside tile groups: Run(2), single rounds, guarded
-// rounds), with the single-stream counter region.  A renderer whose tile
-// groups use the lists takes them for every round: a tile-local shade's
-// TileOrder would leave the slots permuted within their tiles against the
-// positions, and the class lists' gathers by slot lose their coherence
-// (C2 -4 % measured, profiles/r05_exp2).
-static int ClassListShade(pt_device* d, pt_basic_renderer* r, const ptd::dslots& L, const ptd::dframe& F,
-                          const ptd::dparams& P, hipStream_t st)
-{
-    if (int e = ClassListBuffers(d, r, 1)) return e;
-    const size_t nc = (size_t)ptd::PT_OUTCOME_CLASSES * CQ_SUB;
-    uint32_t* cnt = r->cq_counts.ptr + PT_MAX_SPLIT * 2 * nc;
-    uint32_t* cq = cnt + nc * r->cq_parity;
-    uint32_t* cq_next = cnt + nc * (r->cq_parity ^ 1u);
-    r->cq_parity ^= 1u;
-    PT_HIP(pt_launch_shade_classq(r->scene->d, L, F, P, ShadeMats(r), ShadeCompact(r), cq, cq_next, r->cq_list.ptr,
-                                  st));
-    return 0;
-}
-
-int ptRunBasicRenderer(pt_device* d, pt_basic_renderer* r, uint32_t rounds)
-{
-    if (!d) { SetError("null device"); return -1; }
-    if (CheckReady(r) != 0) return -1;
-    PT_HIP(hipSetDevice(d->id));
-    if (Masked(r) && r->active_tiles == 0) {   // nothing to launch: the call still takes its seed
-        r->params.FrameIndex += 1;
-        return 0;
-    }
-    if (int e = EnsureSpill(r)) return e;
-    if (int e = SyncRecordForm(d, r)) return e;
-    if (Masked(r))
-        if (int e = EnsureOrderGroups(d, r, 1)) return e;
-    r->params.FrameIndex += 1;
-    ptd::dparams P = Params(r, r->params.FrameIndex);
-    ptd::dframe F = Frame(r);
-    const ptd::dslots L = ActiveSlots(r);
-    // A masked renderer keeps the natural order (no longest-first re-sort:
-    // tile_order_kernel permutes whole segments).
-    const bool resort = !Masked(r);
-    const bool fused = RoundFused(r, L);
-    // Run(R >= 2) where round batches apply (RunRounds' rule): the R rounds
-    // with the one seed as batches of the rounds kernel (seed_step 0), one
-    // launch instead of R -- the application's Run(2) after a restart.
-    const uint32_t B = r->round_batch ? r->round_batch : (fused && r->fused == 1 ? AUTO_BATCH : 1u);
-    if (fused && rounds >= 2 && B >= 2 && pt_rounds_available(L)) {
-        for (uint32_t left = rounds; left > 0;) {
-            const uint32_t n = std::min(left, B);
-            ptd::dparams Pb = P;
-            Pb.rounds = n;
-            Pb.seed_step = 0;
-            const uint64_t t = d->run_tick % d->profile_period;
-            const bool sampled = d->profiling && (t == 0 || t + n > d->profile_period);
-            d->run_tick += n;
-            event_pair ep{};
-            if (int e = BeginTimed(d, PT_KERNEL_ROUNDS, ep, sampled, n)) return e;
-            PT_HIP(pt_launch_rounds(r->scene->d, L, F, Pb, ShadeMats(r), d->stream));
-            if (int e = EndTimed(d, ep)) return e;
-            for (uint32_t g = 0; resort && g < r->order_groups; g++)
-                PT_HIP(pt_launch_tile_order(L, d->stream, r->order_groups, g));
-            r->rays += RoundSlots(r) * n;
-            left -= n;
-        }
-        return 0;
-    }
-    for (uint32_t i = 0; i < rounds; i++) {
-        // Kernel timing samples every profile_period-th round.
-        const bool sampled = d->profiling && (d->run_tick++ % d->profile_period) == 0;
-        // Tiles keep their relative cost for many rounds: re-sort every
-        // TILE_ORDER_PERIOD rounds (one small launch).
-        const bool sort = L.order && (r->order_tick++ % TILE_ORDER_PERIOD) == 0 && resort;
-        event_pair ep{};
-        if (fused) {
-            if (int e = BeginTimed(d, PT_KERNEL_ROUND, ep, sampled)) return e;
-            PT_HIP(pt_launch_round(r->scene->d, L, F, P, ShadeMats(r), d->stream));
-            if (int e = EndTimed(d, ep)) return e;
-        } else {
-            if (int e = BeginTimed(d, PT_KERNEL_EXTEND, ep, sampled)) return e;
-            PT_HIP(pt_launch_extend(r->scene->d, L, F, L.spill, d->stream));
-            if (int e = EndTimed(d, ep)) return e;
-            if (int e = BeginTimed(d, PT_KERNEL_SHADE, ep, sampled)) return e;
-            if (ClassListRounds(r)) {
-                if (int e = ClassListShade(d, r, L, F, P, d->stream)) return e;
-            } else {
-                PT_HIP(pt_launch_shade(r->scene->d, L, F, P, ShadeMats(r), ShadeCompact(r), d->stream));
-            }
-            if (int e = EndTimed(d, ep)) return e;
-        }
-        if (sort)
-            for (uint32_t g = 0; g < r->order_groups; g++) PT_HIP(pt_launch_tile_order(L, d->stream, r->order_groups, g));
-        r->rays += RoundSlots(r);
-    }
-    return 0;
-}
-
 // Tile groups on concurrent streams (ptSetBasicRendererSplit).  A batch of
 // consecutive rounds over a whole frame ends each extend and shade launch
 // with a tail of a few long blocks while most CUs idle.  Split into K groups
@@ -1509,77 +1397,242 @@ static int EnsureGroupStreams(pt_device* d, uint32_t K)
     return 0;
 }
 
-// k consecutive rounds (FrameIndex + 1 ... + k) in K tile groups.  Group 0
-// runs on the device stream (its launches are the ones profiling times);
-// the others wait for everything enqueued before (fork) and the device
-// stream waits for them at the end (join), on every path out.
-static int RunRoundsSplit(pt_device* d, pt_basic_renderer* r, uint64_t k, uint32_t K)
+// --- the render loop ------------------------------------------------------------
+// Every entry point (ptRunBasicRenderer, ptRunBasicRendererRounds,
+// ptRenderFrame) issues its rounds through the functions below: BeginRounds
+// once per call, then IssueRound per round and view (single-stream rounds,
+// the tile groups of SplitRounds, RunGuardedRounds) or IssueBatch per launch
+// of the rounds kernel.
+
+// The class-list counters and list of one round.
+struct class_lists { uint32_t *counts, *next_counts, *list; };
+
+// Class-list counter regions: g of the K > 1 tile groups a batch runs in, or
+// the single-stream region PT_MAX_SPLIT (K = 1: the renderer's rounds outside
+// tile groups -- Run(2), single rounds, guarded rounds).  A round takes its
+// region's counters of the current parity (zero at the launch), clears the
+// other parity's for the next round, and flips the parity.
+static int NextClassLists(pt_device* d, pt_basic_renderer* r, uint32_t K, uint32_t g, class_lists& q)
 {
+    if (int e = ClassListBuffers(d, r, K)) return e;
+    const size_t nc = (size_t)ptd::PT_OUTCOME_CLASSES * CQ_SUB;
+    const uint32_t region = K > 1 ? g : PT_MAX_SPLIT;
+    uint32_t* cnt = r->cq_counts.ptr + region * 2 * nc;
+    uint32_t& parity = r->cq_parity[region];
+    q.counts = cnt + nc * parity;
+    q.next_counts = cnt + nc * (parity ^ 1u);
+    q.list = r->cq_list.ptr + (K > 1 ? g * ClassListStride(r->slots.tile_count, K) : 0);
+    parity ^= 1u;
+    return 0;
+}
+
+// A batch in K tile groups starts from zeroed group counters at parity 0
+// (the single-stream region keeps itself zero by its own parity).
+static int ResetGroupLists(pt_device* d, pt_basic_renderer* r, uint32_t K)
+{
+    if (int e = ClassListBuffers(d, r, K)) return e;
+    PT_HIP(hipMemsetAsync(r->cq_counts.ptr, 0, PT_MAX_SPLIT * 2 * ptd::PT_OUTCOME_CLASSES * CQ_SUB * sizeof(uint32_t),
+                          d->stream));
+    for (uint32_t g = 0; g < PT_MAX_SPLIT; g++) r->cq_parity[g] = 0;
+    return 0;
+}
+
+// What the rounds of one call share.
+struct round_setup {
+    bool idle;          // an active tile set without a tile: nothing to launch
+    ptd::dframe F;
+    uint32_t mats;      // ShadeMats
+    bool compact;       // ShadeCompact
+    bool fused;         // a round is one round_kernel launch (single-stream rounds only)
+    bool lists;         // an unfused round shades through class lists
+};
+
+// Before the rounds of a call that run in K tile groups (1: on the device
+// stream alone): the device, the spill buffer, the live paths' record form,
+// the order array's group structure (a single-stream round needs one group
+// only under a mask: its launches then cover the head of the array) and the
+// groups' streams.  A masked renderer without an active tile launches
+// nothing: the call still takes its `seeds` seeds.
+static int BeginRounds(pt_device* d, pt_basic_renderer* r, uint32_t K, uint64_t seeds, round_setup& S)
+{
+    S = {};
     PT_HIP(hipSetDevice(d->id));
+    S.idle = Masked(r) && r->active_tiles == 0;
+    if (S.idle) {
+        r->params.FrameIndex += (uint32_t)seeds;
+        return 0;
+    }
     if (int e = EnsureSpill(r)) return e;
     if (int e = SyncRecordForm(d, r)) return e;
-    if (int e = EnsureOrderGroups(d, r, K)) return e;
-    if (int e = EnsureGroupStreams(d, K)) return e;
-    const ptd::dframe F = Frame(r);
-    const uint32_t mats = ShadeMats(r);
-    const bool compact = ShadeCompact(r);
+    if (K > 1 || Masked(r))
+        if (int e = EnsureOrderGroups(d, r, K)) return e;
+    if (K > 1)
+        if (int e = EnsureGroupStreams(d, K)) return e;
+    S.F = Frame(r);
+    S.mats = ShadeMats(r);
+    S.compact = ShadeCompact(r);
+    S.fused = K == 1 && RoundFused(r, ActiveSlots(r));
+    // A renderer whose tile groups use the lists takes them for every round:
+    // a tile-local shade's TileOrder would leave the slots permuted within
+    // their tiles against the positions, and the class lists' gathers by slot
+    // lose their coherence (C2 -4 % measured, profiles/r05_exp2).
+    S.lists = !S.fused && ClassLists(r) && (K > 1 || SplitGroups(r) > 1);
+    return 0;
+}
+
+// What the next round does besides its launches: whether kernel timing
+// samples it (every profile_period-th round) and whether the tile order is
+// re-sorted after it -- tiles keep their relative cost for many rounds, so
+// every TILE_ORDER_PERIOD rounds (one small launch per group); a masked
+// renderer keeps the natural order (tile_order_kernel permutes whole
+// segments).
+struct round_tick { bool sampled, sort; };
+
+static round_tick NextRound(const pt_device* d, const pt_basic_renderer* r)
+{
+    return {d->profiling && d->run_tick % d->profile_period == 0,
+            r->slots.order && r->order_tick % TILE_ORDER_PERIOD == 0 && !Masked(r)};
+}
+
+// Host bookkeeping of n single rounds that ran, `seeds` of them with a seed
+// of their own, each over `slots` paths.
+static void RoundsDone(pt_device* d, pt_basic_renderer* r, uint32_t n, uint32_t seeds, uint64_t slots)
+{
+    r->params.FrameIndex += seeds;
+    r->rays += slots * n;
+    d->run_tick += n;
+    if (r->slots.order) r->order_tick += n;
+}
+
+// Longest-first re-sort of the order array's groups g0 .. g1 - 1 on st.
+static int Resort(pt_basic_renderer* r, uint32_t g0, uint32_t g1, hipStream_t st)
+{
+    for (uint32_t g = g0; g < g1; g++) PT_HIP(pt_launch_tile_order(r->slots, st, r->order_groups, g));
+    return 0;
+}
+
+// One round's launches over the view L -- every tile, the active ones, group
+// g of K, with or without a guard -- on st: the fused round, or extend and
+// then the tile-local or the class-list shade.  timed: kernel timing takes
+// the launches (those on the device stream of a sampled round).
+static int IssueRound(pt_device* d, pt_basic_renderer* r, const round_setup& S, const ptd::dslots& L,
+                      const ptd::dparams& P, hipStream_t st, bool timed, uint32_t K = 1, uint32_t g = 0)
+{
+    event_pair ep{};
+    if (S.fused) {
+        if (int e = BeginTimed(d, PT_KERNEL_ROUND, ep, timed)) return e;
+        PT_HIP(pt_launch_round(r->scene->d, L, S.F, P, S.mats, st));
+        return EndTimed(d, ep);
+    }
+    if (int e = BeginTimed(d, PT_KERNEL_EXTEND, ep, timed)) return e;
+    PT_HIP(pt_launch_extend(r->scene->d, L, S.F, L.spill, st));
+    if (int e = EndTimed(d, ep)) return e;
+    if (int e = BeginTimed(d, PT_KERNEL_SHADE, ep, timed)) return e;
+    if (S.lists) {
+        class_lists q;
+        if (int e = NextClassLists(d, r, K, g, q)) return e;
+        PT_HIP(pt_launch_shade_classq(r->scene->d, L, S.F, P, S.mats, S.compact, q.counts, q.next_counts, q.list, st,
+                                      r->slots.tile_count, K, g));
+    } else {
+        PT_HIP(pt_launch_shade(r->scene->d, L, S.F, P, S.mats, S.compact, st));
+    }
+    return EndTimed(d, ep);
+}
+
+// One launch of the rounds kernel: n rounds over L, round i with the seed
+// first_seed + i * seed_step.  The profiling period counts rounds: the batch
+// is timed when one of its n rounds is a sampled one.  The batch's block
+// times order the next batch (natural order under a mask).
+static int IssueBatch(pt_device* d, pt_basic_renderer* r, const round_setup& S, const ptd::dslots& L,
+                      uint32_t first_seed, uint32_t seed_step, uint32_t n)
+{
+    ptd::dparams P = Params(r, first_seed);
+    P.rounds = n;
+    P.seed_step = seed_step;
+    const uint64_t t = d->run_tick % d->profile_period;
+    const bool sampled = d->profiling && (t == 0 || t + n > d->profile_period);
+    d->run_tick += n;
+    event_pair ep{};
+    if (int e = BeginTimed(d, PT_KERNEL_ROUNDS, ep, sampled, n)) return e;
+    PT_HIP(pt_launch_rounds(r->scene->d, L, S.F, P, S.mats, d->stream));
+    if (int e = EndTimed(d, ep)) return e;
+    if (!Masked(r))
+        if (int e = Resort(r, 0, r->order_groups, d->stream)) return e;
+    r->rays += RoundSlots(r) * n;
+    return 0;
+}
+
+int ptRunBasicRenderer(pt_device* d, pt_basic_renderer* r, uint32_t rounds)
+{
+    if (!d) { SetError("null device"); return -1; }
+    if (CheckReady(r) != 0) return -1;
+    round_setup S;
+    if (int e = BeginRounds(d, r, 1, 1, S)) return e;
+    if (S.idle) return 0;
+    r->params.FrameIndex += 1;   // the call's one seed, whatever its rounds
+    const uint32_t seed = r->params.FrameIndex;
+    const ptd::dslots L = ActiveSlots(r);
+    // Run(R >= 2) of a renderer whose rounds fuse: the R rounds with the one
+    // seed as batches of the rounds kernel (seed_step 0), one launch instead
+    // of R -- the application's Run(2) after a restart.  (RunRounds batches
+    // for an explicit round_batch without fused rounds too.)
+    const uint32_t B = r->round_batch ? r->round_batch : (S.fused && r->fused == 1 ? AUTO_BATCH : 1u);
+    if (S.fused && rounds >= 2 && B >= 2 && pt_rounds_available(L)) {
+        for (uint32_t left = rounds; left > 0;) {
+            const uint32_t n = std::min(left, B);
+            if (int e = IssueBatch(d, r, S, L, seed, 0, n)) return e;
+            left -= n;
+        }
+        return 0;
+    }
+    const ptd::dparams P = Params(r, seed);
+    for (uint32_t i = 0; i < rounds; i++) {
+        const round_tick tick = NextRound(d, r);
+        if (int e = IssueRound(d, r, S, L, P, d->stream, tick.sampled)) return e;
+        if (tick.sort)
+            if (int e = Resort(r, 0, r->order_groups, d->stream)) return e;
+        RoundsDone(d, r, 1, 0, RoundSlots(r));
+    }
+    return 0;
+}
+
+// Tile groups on concurrent streams: k consecutive rounds (FrameIndex + 1 ...
+// + k) in K > 1 tile groups, after BeginRounds for K.  Group 0 runs on the
+// device stream (its launches are the ones profiling times); the others wait
+// for everything enqueued before (fork) and the device stream waits for them
+// at the end (join), on every path out.  Group g's segment is re-sorted on
+// group g's stream.
+static int SplitRounds(pt_device* d, pt_basic_renderer* r, const round_setup& S, uint64_t k, uint32_t K)
+{
     ptd::dslots G[PT_MAX_SPLIT];
-    hipStream_t S[PT_MAX_SPLIT];
+    hipStream_t St[PT_MAX_SPLIT];
     for (uint32_t g = 0; g < K; g++) {
         G[g] = r->slots;
         G[g].order = r->slots.order + pt_tile_group_start(r->slots.tile_count, K, g);
         G[g].tile_count = Masked(r) ? r->group_active[g] : pt_tile_group_count(r->slots.tile_count, K, g);
-        S[g] = g ? d->group_stream[g - 1] : d->stream;
+        St[g] = g ? d->group_stream[g - 1] : d->stream;
     }
-    const bool lists = ClassLists(r);
-    if (lists) {
-        // Per group: 2 parities x classes counters (zero at the batch
-        // start) and a list region of ClassListStride words.
-        if (int e = ClassListBuffers(d, r, K)) return e;
-        PT_HIP(hipMemsetAsync(r->cq_counts.ptr, 0, PT_MAX_SPLIT * 2 * ptd::PT_OUTCOME_CLASSES * CQ_SUB * sizeof(uint32_t),
-                              d->stream));
-    }
+    if (S.lists)
+        if (int e = ResetGroupLists(d, r, K)) return e;
     PT_HIP(hipEventRecord(d->fork_event, d->stream));
-    for (uint32_t g = 1; g < K; g++) PT_HIP(hipStreamWaitEvent(S[g], d->fork_event, 0));
+    for (uint32_t g = 1; g < K; g++) PT_HIP(hipStreamWaitEvent(St[g], d->fork_event, 0));
     auto rounds = [&]() -> int {
         for (uint64_t i = 0; i < k; i++) {
-            r->params.FrameIndex += 1;
-            const ptd::dparams P = Params(r, r->params.FrameIndex);
-            const bool sampled = d->profiling && (d->run_tick++ % d->profile_period) == 0;
-            const bool sort = (r->order_tick++ % TILE_ORDER_PERIOD) == 0 && !Masked(r);
+            const ptd::dparams P = Params(r, r->params.FrameIndex + 1);
+            const round_tick tick = NextRound(d, r);
             for (uint32_t g = 0; g < K; g++) {
                 if (G[g].tile_count == 0) continue;   // a group without an active tile
-                event_pair ep{};
-                if (g == 0)
-                    if (int e = BeginTimed(d, PT_KERNEL_EXTEND, ep, sampled)) return e;
-                PT_HIP(pt_launch_extend(r->scene->d, G[g], F, r->slots.spill, S[g]));
-                if (g == 0) {
-                    if (int e = EndTimed(d, ep)) return e;
-                    if (int e = BeginTimed(d, PT_KERNEL_SHADE, ep, sampled)) return e;
-                }
-                if (lists) {
-                    // Class-pure shade: the group's own counters (parity per
-                    // round) and list region.
-                    const size_t nc = (size_t)ptd::PT_OUTCOME_CLASSES * CQ_SUB;
-                    uint32_t* cnt = r->cq_counts.ptr + g * 2 * nc;
-                    PT_HIP(pt_launch_shade_classq(r->scene->d, G[g], F, P, mats, compact, cnt + nc * (i & 1u),
-                                                  cnt + nc * ((i & 1u) ^ 1u),
-                                                  r->cq_list.ptr + g * ClassListStride(r->slots.tile_count, K), S[g],
-                                                  r->slots.tile_count, K, g));
-                } else {
-                    PT_HIP(pt_launch_shade(r->scene->d, G[g], F, P, mats, compact, S[g]));
-                }
-                if (g == 0)
-                    if (int e = EndTimed(d, ep)) return e;
-                if (sort) PT_HIP(pt_launch_tile_order(r->slots, S[g], K, g));
+                if (int e = IssueRound(d, r, S, G[g], P, St[g], g == 0 && tick.sampled, K, g)) return e;
+                if (tick.sort)
+                    if (int e = Resort(r, g, g + 1, St[g])) return e;
             }
-            r->rays += RoundSlots(r);
+            RoundsDone(d, r, 1, 1, RoundSlots(r));
         }
         return 0;
     };
     const int rc = rounds();
     for (uint32_t g = 1; g < K; g++) {
-        PT_HIP(hipEventRecord(d->join_event[g - 1], S[g]));
+        PT_HIP(hipEventRecord(d->join_event[g - 1], St[g]));
         PT_HIP(hipStreamWaitEvent(d->stream, d->join_event[g - 1], 0));
     }
     return rc;
@@ -1587,57 +1640,35 @@ static int RunRoundsSplit(pt_device* d, pt_basic_renderer* r, uint64_t k, uint32
 
 // k consecutive Run(1) calls: the same rounds with the same seeds (FrameIndex
 // + 1 ... + k), as round batches (rounds_kernel) when the renderer allows
-// them, else one ptRunBasicRenderer(1) per round.  round_batch: 0 automatic
-// (AUTO_BATCH rounds per launch when every tile fits on the GPU at once, where
-// the per-round launches cost most: C1 256x256 round 0.0176 -> 0.0055 ms;
-// whole frames that do not fit run slower batched -- C3 0.431 vs 0.47-0.53
-// ms per round, C2 -22 %: extend then runs at the shade kernel's occupancy and
-// the block's waves wait at the round's barriers), 1 never, R >= 2 always R.
+// them, else in tile groups (SplitGroups; two rounds or more), else one
+// ptRunBasicRenderer(1) per round.  round_batch: 0 automatic (AUTO_BATCH
+// rounds per launch when every tile fits on the GPU at once, where the
+// per-round launches cost most: C1 256x256 round 0.0176 -> 0.0055 ms; whole
+// frames that do not fit run slower batched -- C3 0.431 vs 0.47-0.53 ms per
+// round, C2 -22 %: extend then runs at the shade kernel's occupancy and the
+// block's waves wait at the round's barriers), 1 never, R >= 2 always R.
+// A scene that needs a spilled stack takes no batches (pt_rounds_available).
 static int RunRounds(pt_device* d, pt_basic_renderer* r, uint64_t k)
 {
     if (!r || CheckReady(r) != 0) return -1;
-    if (Masked(r) && r->active_tiles == 0) {   // nothing to launch: the rounds still take their seeds
-        r->params.FrameIndex += k;
-        return 0;
-    }
     uint32_t B = r->round_batch;
     if (B == 0) B = RoundFused(r, ActiveSlots(r)) && r->fused == 1 ? AUTO_BATCH : 1u;
-    if (B > 1) {
-        PT_HIP(hipSetDevice(d->id));
-        if (int e = EnsureSpill(r)) return e;
-        if (int e = SyncRecordForm(d, r)) return e;
-        if (pt_rounds_available(r->slots)) {
-            if (Masked(r))
-                if (int e = EnsureOrderGroups(d, r, 1)) return e;
-            const ptd::dslots L = ActiveSlots(r);
-            const ptd::dframe F = Frame(r);
-            while (k > 0) {
-                const uint32_t n = (uint32_t)std::min<uint64_t>(k, B);
-                ptd::dparams P = Params(r, r->params.FrameIndex + 1);
-                P.rounds = n;
-                P.seed_step = 1;
-                r->params.FrameIndex += n;
-                // The profiling period counts rounds: a batch is timed when
-                // one of its n rounds is a sampled one.
-                const uint64_t t = d->run_tick % d->profile_period;
-                const bool sampled = d->profiling && (t == 0 || t + n > d->profile_period);
-                d->run_tick += n;
-                event_pair ep{};
-                if (int e = BeginTimed(d, PT_KERNEL_ROUNDS, ep, sampled, n)) return e;
-                PT_HIP(pt_launch_rounds(r->scene->d, L, F, P, ShadeMats(r), d->stream));
-                if (int e = EndTimed(d, ep)) return e;
-                // The batch's block times order the next batch (natural
-                // order under a mask).
-                for (uint32_t g = 0; !Masked(r) && g < r->order_groups; g++)
-                    PT_HIP(pt_launch_tile_order(r->slots, d->stream, r->order_groups, g));
-                r->rays += RoundSlots(r) * n;
-                k -= n;
-            }
-            return 0;
+    const bool batches = B > 1 && !Spills(r);
+    const uint32_t K = batches || k < 2 ? 1u : SplitGroups(r);
+    round_setup S;
+    if (int e = BeginRounds(d, r, K, k, S)) return e;
+    if (S.idle) return 0;
+    if (batches) {
+        const ptd::dslots L = ActiveSlots(r);
+        while (k > 0) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(k, B);
+            if (int e = IssueBatch(d, r, S, L, r->params.FrameIndex + 1, 1, n)) return e;
+            r->params.FrameIndex += n;
+            k -= n;
         }
+        return 0;
     }
-    const uint32_t K = SplitGroups(r);
-    if (K > 1 && k > 1) return RunRoundsSplit(d, r, k, K);
+    if (K > 1) return SplitRounds(d, r, S, k, K);
     for (uint64_t i = 0; i < k; i++)
         if (int e = ptRunBasicRenderer(d, r, 1)) return e;
     return 0;
@@ -1778,49 +1809,31 @@ int ptGetStats(pt_device* d, pt_basic_renderer* r, uint64_t* rays, uint64_t* sam
 
 // n guarded Run(1) rounds (FrameIndex + 1 ... + n) on the device stream:
 // each preceded by guard_kernel, the launches of a round past the target
-// returning at once.  Returns the rounds that ran in *ran and leaves
-// FrameIndex and the ray count as those rounds left them.
+// returning at once.  Untimed, no re-sort.  Returns the rounds that ran in
+// *ran; the host's bookkeeping -- the seeds, the rays of every valid slot,
+// the ticks and the class-list parity -- follows those rounds, not the n
+// issued.  (Never masked: ptRenderFrame refuses an active tile set.)
 static int RunGuardedRounds(pt_device* d, pt_basic_renderer* r, uint32_t n, uint64_t target, uint32_t* ran)
 {
-    PT_HIP(hipSetDevice(d->id));
-    if (int e = EnsureSpill(r)) return e;
-    if (int e = SyncRecordForm(d, r)) return e;
+    round_setup S;
+    if (int e = BeginRounds(d, r, 1, 0, S)) return e;
     if (!r->guard.ptr) PT_HIP(r->guard.alloc(2));
     PT_HIP(hipMemsetAsync(r->guard.ptr, 0, 2 * sizeof(uint32_t), d->stream));
     ptd::dslots L = r->slots;
     L.stop = r->guard.ptr;
-    const ptd::dframe F = Frame(r);
-    const bool fused = RoundFused(r, L);
-    const uint32_t mats = ShadeMats(r);
-    const bool compact = ShadeCompact(r);
-    const uint64_t base = r->params.FrameIndex;
-    const bool lists = !fused && ClassListRounds(r);
-    const uint32_t parity0 = r->cq_parity;
+    const uint32_t base = r->params.FrameIndex;
+    uint32_t& parity = r->cq_parity[PT_MAX_SPLIT];
+    const uint32_t parity0 = parity;
     for (uint32_t i = 0; i < n; i++) {
         PT_HIP(pt_launch_guard(r->done.ptr, r->slots.n / 64 + 1, target, r->guard.ptr, d->stream));
-        const ptd::dparams P = Params(r, base + i + 1);
-        if (fused) {
-            PT_HIP(pt_launch_round(r->scene->d, L, F, P, mats, d->stream));
-        } else {
-            PT_HIP(pt_launch_extend(r->scene->d, L, F, L.spill, d->stream));
-            if (lists) {
-                if (int e = ClassListShade(d, r, L, F, P, d->stream)) return e;
-            } else {
-                PT_HIP(pt_launch_shade(r->scene->d, L, F, P, mats, compact, d->stream));
-            }
-        }
+        if (int e = IssueRound(d, r, S, L, Params(r, base + i + 1), d->stream, false)) return e;
     }
     uint32_t flags[2] = {0, 0};
     PT_WAIT(d);
     PT_HIP(hipMemcpy(flags, r->guard.ptr, sizeof(flags), hipMemcpyDeviceToHost));
     *ran = flags[1];
-    // A skipped round left the class-list counters alone: the parity
-    // follows the rounds that ran.
-    if (lists) r->cq_parity = parity0 ^ (flags[1] & 1u);
-    r->params.FrameIndex = base + flags[1];
-    r->rays += r->valid_slots * flags[1];
-    d->run_tick += flags[1];
-    r->order_tick += flags[1];
+    if (S.lists) parity = parity0 ^ (*ran & 1u);   // a skipped round left the class-list counters alone
+    RoundsDone(d, r, *ran, *ran, r->valid_slots);
     return 0;
 }
 
@@ -1928,13 +1941,10 @@ int ptReadBasicRendererStreamState(pt_device* d, pt_basic_renderer* r, uint32_t 
         dbuf<float2> ruv;
         PT_HIP(rec.alloc(n));
         PT_HIP(ruv.alloc(n));
-        hipError_t e = pt_launch_finalize(r->scene->d, n, r->hit.ptr, r->uv.ptr, rec.ptr, ruv.ptr, d->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-        if (e == hipSuccess) e = hipMemcpy(hit.data(), rec.ptr, (size_t)n * 16, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(uv.data(), ruv.ptr, (size_t)n * 8, hipMemcpyDeviceToHost);
-        rec.release();
-        ruv.release();
-        PT_HIP(e);
+        PT_HIP(pt_launch_finalize(r->scene->d, n, r->hit.ptr, r->uv.ptr, rec.ptr, ruv.ptr, d->stream));
+        PT_HIP(hipStreamSynchronize(d->stream));
+        PT_HIP(hipMemcpy(hit.data(), rec.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
+        PT_HIP(hipMemcpy(uv.data(), ruv.ptr, (size_t)n * 8, hipMemcpyDeviceToHost));
     }
     PT_HIP(hipMemcpy(ray.data(), r->ray.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
     PT_HIP(hipMemcpy(thr.data(), r->thr.ptr, (size_t)n * 16, hipMemcpyDeviceToHost));
@@ -2049,15 +2059,10 @@ int ptWriteBasicRendererStreamState(pt_device* d, pt_basic_renderer* r, uint32_t
     PT_HIP(hipMemcpy(r->lam.ptr + s0, lam.data(), n * 4, hipMemcpyHostToDevice));
     PT_HIP(hipMemcpy(r->act.ptr + s0, act.data(), n * 8, hipMemcpyHostToDevice));
     dbuf<float4> stage;
-    hipError_t e = stage.upload(ray.data(), n);
-    if (e == hipSuccess) e = pt_launch_restore_rays(r->slots, Frame(r), stage.ptr, s0 / 256, T, d->stream);
-    if (e != hipSuccess) {
-        stage.release();
-        PT_HIP(e);
-    }
-    const int w = DeviceWait(d);
-    stage.release();
-    return w;
+    PT_HIP(stage.upload(ray.data(), n));
+    PT_HIP(pt_launch_restore_rays(r->slots, Frame(r), stage.ptr, s0 / 256, T, d->stream));
+    PT_WAIT(d);   // the launch reads stage
+    return 0;
 }
 
 int ptWriteBasicRendererState(pt_device* d, pt_basic_renderer* r, const pt_pixel_state* in)
@@ -2118,17 +2123,13 @@ pt_preview* ptCreatePreviewRenderContext(pt_device* d, pt_scene* s)
     c->dev = d;
     c->scene = s;
     uint32_t none = 0xFFFFFFFFu;
-    if (hipMalloc(&c->query, sizeof(uint32_t)) != hipSuccess ||
-        hipMemcpy(c->query, &none, sizeof(none), hipMemcpyHostToDevice) != hipSuccess) {
+    if (c->query.upload(&none, 1) != hipSuccess) {
         SetError("preview query buffer allocation failed");
-        if (c->query) (void)hipFree(c->query);
         delete c;
         return nullptr;
     }
     if (c->observe.alloc(PT_OBSERVE_TABLE_FLOATS) != hipSuccess || pt_launch_observe_table(c->observe.ptr, d->stream) != hipSuccess) {
         SetError("preview table set-up failed");
-        c->observe.release();
-        (void)hipFree(c->query);
         delete c;
         return nullptr;
     }
@@ -2139,11 +2140,6 @@ void ptDestroyPreviewRenderContext(pt_device* d, pt_preview* c)
 {
     if (!c) return;
     if (d) (void)hipSetDevice(d->id);
-    c->image.release();
-    c->aov.release();
-    c->spill.release();
-    c->observe.release();
-    if (c->query) (void)hipFree(c->query);
     delete c;
 }
 
@@ -2169,7 +2165,7 @@ int ptRenderPreview(pt_device* d, pt_preview* c, const pt_preview_parameters* p)
         spill = c->spill.ptr;
     }
     PT_TIMED(d, PT_KERNEL_PREVIEW,
-             pt_launch_preview(c->scene->d, p, spill, c->image.ptr, c->aov.ptr, c->query, c->observe.ptr, d->stream));
+             pt_launch_preview(c->scene->d, p, spill, c->image.ptr, c->aov.ptr, c->query.ptr, c->observe.ptr, d->stream));
     c->width = p->RenderSizeX;
     c->height = p->RenderSizeY;
     c->rendered = true;
@@ -2181,7 +2177,7 @@ int ptRetrievePreviewQueryResult(pt_device* d, pt_preview* c, uint32_t* hit_shap
 {
     if (!d || !c || !hit_shape_index) { SetError("null argument"); return -1; }
     PT_HIP(hipSetDevice(d->id));
-    PT_HIP(hipMemcpyAsync(hit_shape_index, c->query, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    PT_HIP(hipMemcpyAsync(hit_shape_index, c->query.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
     PT_WAIT(d);
     return 0;
 }
@@ -2225,8 +2221,6 @@ pt_denoise_guides* ptCreateDenoiseGuides(pt_device* d, uint32_t w, uint32_t h)
         pt_launch_observe_table(g->observe.ptr, d->stream) != hipSuccess ||
         hipStreamSynchronize(d->stream) != hipSuccess) {
         SetError("denoise guides allocation failed (%zu bytes)", n * sizeof(pt_denoise_guide));
-        g->records.release();
-        g->observe.release();
         delete g;
         return nullptr;
     }
@@ -2237,10 +2231,6 @@ void ptDestroyDenoiseGuides(pt_device* d, pt_denoise_guides* g)
 {
     if (!g) return;
     if (d) (void)hipSetDevice(d->id);
-    g->records.release();
-    g->scratch.release();
-    g->spill.release();
-    g->observe.release();
     delete g;
 }
 
@@ -2481,20 +2471,17 @@ int ptComputeFrameStatistics(pt_device* d, pt_sample_buffer* a, pt_sample_buffer
         return -1;
     }
     PT_HIP(hipSetDevice(d->id));
-    if (!d->stats) {
-        if (hipError_t e = hipMalloc(&d->stats, sizeof(pt_frame_statistics)); e != hipSuccess) {
-            d->stats = nullptr;
-            SetError("frame statistics allocation failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
+    if (hipError_t e = d->stats.alloc(1); e != hipSuccess) {
+        SetError("frame statistics allocation failed: %s", hipGetErrorString(e));
+        return (int)e;
     }
     const uint64_t n = (uint64_t)a->width * a->height;
-    PT_HIP(hipMemsetAsync(d->stats, 0, sizeof(pt_frame_statistics), d->stream));
+    PT_HIP(hipMemsetAsync(d->stats.ptr, 0, sizeof(pt_frame_statistics), d->stream));
     PT_TIMED(d, PT_KERNEL_STATS,
              pt_launch_frame_statistics(a->accum, b ? b->accum : nullptr, n, d->cu_count,
-                                        StatsUniform(d->stats_variant), d->stats, d->stream));
+                                        StatsUniform(d->stats_variant), d->stats.ptr, d->stream));
     pt_frame_statistics s;
-    PT_HIP(hipMemcpyAsync(&s, d->stats, sizeof(s), hipMemcpyDeviceToHost, d->stream));
+    PT_HIP(hipMemcpyAsync(&s, d->stats.ptr, sizeof(s), hipMemcpyDeviceToHost, d->stream));
     PT_WAIT(d);
     // The kernel keeps each minimum as the complement of its bit pattern, so
     // that 0 is "no value" for all four fields.
@@ -2593,8 +2580,6 @@ int ptTraceRays(pt_device* d, pt_scene* s, uint32_t n, const float* origins, con
             out[i].v = uv[i].y;
         }
     } while (0);
-    d_o.release(); d_t.release(); d_v.release(); d_spill.release();
-    d_hit.release(); d_rec.release(); d_hc.release(); d_uv.release();
     if (e != hipSuccess) { SetError("ptTraceRays: %s", hipGetErrorString(e)); return (int)e; }
     return 0;
 }
@@ -2636,8 +2621,6 @@ int ptTraceRaysStats(pt_device* d, pt_scene* s, uint32_t n, const float* origins
             break;
         e = hipStreamSynchronize(d->stream);
     } while (0);
-    d_o.release(); d_t.release(); d_v.release(); d_spill.release(); d_steps.release();
-    d_hit.release(); d_hc.release(); d_out.release();
     if (e != hipSuccess) { SetError("ptTraceRaysStats: %s", hipGetErrorString(e)); return (int)e; }
     for (int i = 0; i < PT_EXTEND_STATS_COUNT; i++) out[i] = h[i];
     return 0;

@@ -2,7 +2,7 @@
 configs' full sizes (VERDICT r05, next-round task 1).
 
 The headline runs ptRenderFrame on the C3 frame at 1920x1080.  Its rounds
-run in three tile groups on concurrent HIP streams (RunRoundsSplit).  On C2
+run in three tile groups on concurrent HIP streams (SplitRounds).  On C2
 and C5 the groups shade through per-class lists (shade_classq_kernel).
 Nothing here forces a mode: every renderer keeps the product defaults, and
 each test asserts that the defaults take the path under test.  Each is then

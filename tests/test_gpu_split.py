@@ -316,3 +316,44 @@ def test_class_lists_uneven_groups_and_single_rounds(pt, dev, config, W, H):
     r.close()
     sb.close()
     ds.close()
+
+
+def test_class_list_parity_after_guarded_frame_end(pt, dev):
+    """The class-list counter parity handed from guarded rounds to the other
+    two list paths.  A 3-spp frame of C2 at 160x128 in three groups ends
+    through four guarded single-stream rounds, the last skipped on the device
+    (8 rounds in all), so the single-stream parity follows an odd number of
+    rounds out of an even number issued.  Single-stream list rounds, a split
+    batch and another single round continue on the same renderer without a
+    Reset: the same bits as the oracle's Reset, Run(2), Run(1) ... over as
+    many rounds."""
+    W, H, spp = 160, 128, 3
+    s = scene_for(pt, 2)
+    ds = pt.DeviceScene(dev)
+    ds.update(s)
+    sb = pt.SampleBuffer(dev, W, H)
+    r = pt.BasicRenderer(dev, ds, sb)
+    r.RenderFlags = s.info.render_flags
+    r.PathTerminationProbability = s.info.termination_probability
+    r.set_fused_rounds(0)
+    r.set_split(3)
+    assert r.class_lists()
+    rounds, samples = r.render_frame(spp * W * H)
+    assert samples >= spp * W * H and rounds > 2
+    r.run(1)
+    r.run_rounds(4)
+    r.run(1)
+    dev.synchronize()
+    got = r.read_state(), sb.read(), r.stats()
+    r.close()
+    sb.close()
+    ds.close()
+    o = oracle_lib.OracleRenderer(s.packs(), W, H)
+    o.RenderFlags = s.info.render_flags
+    o.PathTerminationProbability = s.info.termination_probability
+    o.reset()
+    o.run(2)
+    for _ in range(rounds + 6 - 2):
+        o.run(1)
+    same(got, (o.state(), o.accum(), o.counters()))
+    o.close()
