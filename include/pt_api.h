@@ -111,7 +111,7 @@ enum {
     PT_KERNEL_DENOISE = 7,   /* one a-trous iteration of ptDenoiseSampleBuffer */
     PT_KERNEL_GUIDES  = 8,   /* ptRenderDenoiseGuides */
     PT_KERNEL_STATS   = 9,   /* ptComputeFrameStatistics' and ptComputeTileStatistics' passes, ptAccumulateSampleBuffer's add */
-    PT_KERNEL_REPROJECT = 10, /* ptReprojectSampleBuffer, ptReprojectSampleBufferMoving */
+    PT_KERNEL_REPROJECT = 10, /* ptReprojectSampleBuffer, ptReprojectSampleBufferMoving, ptRectifyHistory */
     PT_KERNEL_COUNT   = 11,
 };
 
@@ -516,6 +516,30 @@ int  ptReprojectSampleBufferMoving(pt_device* device, pt_sample_buffer* prev, pt
                                    const pt_packed_camera* camera, const pt_shape_motion* motion,
                                    uint32_t motion_count, const pt_reproject_parameters* params,
                                    pt_sample_buffer* dst);
+/* History validation (no reference counterpart; definition, kernel design and
+ * measured times in DESIGN.md §6 row 11; arithmetic in pt_rectify.h): holds a
+ * carried history against the new frame's own samples, so that shading that
+ * changed without any geometry changing (a shadow that moved, an edited
+ * material or sky) does not keep its weight.  history is an accumulator in
+ * (mean * n, n) form, e.g. a reprojection's output; current is the
+ * accumulator of the new rounds alone; guides are the current view's.  Every
+ * pixel of dst receives the history with its mean colour pulled into
+ * mean +- Sigma standard deviations of the current samples of the window
+ * around it that show the same surface, and, where it had to be pulled, its
+ * count cut to ClampedHistory; a pixel with fewer than MinNeighbours such
+ * samples keeps its bits, one without a usable history becomes 0, 0, 0, 0.
+ * dst is an accumulator again: adding it to current with
+ * ptAccumulateSampleBuffer gives the frame the renderer goes on accumulating
+ * into.  dst == history is
+ * allowed and is the normal use.  Enqueues one launch (counted under
+ * PT_KERNEL_REPROJECT) and returns, like ptReprojectSampleBuffer.  current
+ * and guides are not written; two calls on the same inputs give the same
+ * bits, and the result equals ptsRectifyHistory's (pt_scene.h) bit for bit.
+ * Fails, launching and writing nothing, on a NULL argument, dst == current,
+ * history == current, an object of another device, objects of different
+ * sizes, or a parameter outside its range (pt_packed.h). */
+int  ptRectifyHistory(pt_device* device, pt_sample_buffer* history, pt_sample_buffer* current,
+                      pt_denoise_guides* guides, const pt_rectify_parameters* params, pt_sample_buffer* dst);
 
 /* Frame statistics (no reference counterpart; definition, kernel design and
  * measured times in DESIGN.md §6 row 6; helpers that read the result in

@@ -232,6 +232,17 @@ typedef struct pt_reproject_parameters {
     float    MaxHistory;               /* > 0, default 64 (+inf: none): cap on the carried sample count */
 } pt_reproject_parameters;
 
+/* History validation (arithmetic in pt_rectify.h): the
+ * window of new samples a carried history is held against, how far from
+ * their mean it may lie and what a clipped pixel keeps of its count. */
+typedef struct pt_rectify_parameters {
+    uint32_t Radius;                   /* 1..3, default 3: the window is (2 Radius + 1)^2 pixels */
+    uint32_t MinNeighbours;            /* 1..49, default 25: fewer window members leave the history untested */
+    float    Sigma;                    /* finite, >= 0, default 1: half width of the box in standard deviations */
+    float    ClampedHistory;           /* > 0, default 8 (+inf: no cut): cap on a clipped pixel's sample count */
+    float    NormalCosine;             /* in (-1, 1], default 0.9: smallest dot product with a member's normal */
+} pt_rectify_parameters;
+
 /* One shape's motion between two packed scenes, filled
  * by ptsShapeMotion (pt_scene.h) and read by the moving-shape reprojection
  * (pt_reproject.h).  Point: rows 0..2 of the affine map from the current
@@ -295,6 +306,7 @@ static_assert(sizeof(pt_denoise_guide) == 32, "denoise_guide");
 static_assert(sizeof(pt_denoise_parameters) == 20, "denoise_parameters");
 static_assert(sizeof(pt_denoise_pair_parameters) == 20, "denoise_pair_parameters");
 static_assert(sizeof(pt_reproject_parameters) == 16, "reproject_parameters");
+static_assert(sizeof(pt_rectify_parameters) == 20, "rectify_parameters");
 static_assert(sizeof(pt_shape_motion) == 96, "shape_motion");
 static_assert(sizeof(pt_packed_transform) == 128, "packed_transform");
 static_assert(sizeof(pt_packed_texture) == 32, "packed_texture");

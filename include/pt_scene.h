@@ -235,6 +235,21 @@ int  ptsReprojectMoving(uint32_t prev_width, uint32_t prev_height, const float* 
                         uint32_t height, const pt_denoise_guide* guides, const pt_packed_camera* camera,
                         const pt_shape_motion* motion, uint32_t motion_count, const pt_reproject_parameters* params,
                         float* out_rgba);
+/* History validation on the host (no reference counterpart; definition in
+ * DESIGN.md §6 row 11, arithmetic in pt_rectify.h): the CPU path and the
+ * implementation ptRectifyHistory (pt_api.h) is compared with, bit for bit.
+ * history: an accumulator in (mean * n, n) form, e.g. ptsReproject's output;
+ * current: the accumulator of the new rounds alone; guides: the current
+ * view's records; all width x height.  out_rgba receives the history with
+ * every pixel's mean colour pulled into mean +- Sigma deviations of the
+ * current samples around it that show the same surface, and the count of a
+ * pulled pixel cut to ClampedHistory; pixels that could not be tested keep
+ * their bits, pixels without a usable history become 0, 0, 0, 0.  out_rgba
+ * may be history.  Returns non-zero, leaving out_rgba untouched, on a NULL
+ * argument, an empty image, history == current, out_rgba == current or a
+ * parameter outside its range (pt_packed.h).  Single-threaded. */
+int  ptsRectifyHistory(uint32_t width, uint32_t height, const float* history, const float* current,
+                       const pt_denoise_guide* guides, const pt_rectify_parameters* params, float* out_rgba);
 /* pt_reproject.h's central camera ray of pixel (x, y) of a width x height
  * frame (the guide kernel's ray: pixel centre, lens centre, the velocity
  * after its packed round trip).  Non-zero on a NULL argument, an empty frame

@@ -109,6 +109,19 @@ class pt_reproject_parameters(C.Structure):
     ]
 
 
+class pt_rectify_parameters(C.Structure):
+    """pt_rectify_parameters (include/pt_packed.h)."""
+    _fields_ = [
+        ("Radius", C.c_uint32),
+        ("MinNeighbours", C.c_uint32),
+        ("Sigma", C.c_float),
+        ("ClampedHistory", C.c_float),
+        ("NormalCosine", C.c_float),
+    ]
+
+
+assert C.sizeof(pt_rectify_parameters) == 20
+
 STATS_BINS = 256
 
 
@@ -245,7 +258,7 @@ DENOISE_MAX_ITERATIONS = 8
 DENOISE_VARIANT_AUTO, DENOISE_VARIANT_GATHER, DENOISE_VARIANT_LATTICE = 0, 1, 2
 KERNEL_STATS = 9     # the frame and tile statistics passes and the sample-buffer add (PT_KERNEL_STATS)
 STATS_VARIANT_AUTO, STATS_VARIANT_PLAIN, STATS_VARIANT_UNIFORM = 0, 1, 2
-KERNEL_REPROJECT = 10   # ptReprojectSampleBuffer and ptReprojectSampleBufferMoving (PT_KERNEL_REPROJECT)
+KERNEL_REPROJECT = 10   # ptReprojectSampleBuffer[Moving] and ptRectifyHistory (PT_KERNEL_REPROJECT)
 
 _vp = C.c_void_p
 _u32 = C.c_uint32
@@ -316,6 +329,7 @@ SCENE_API = {
     "ptsShapeMotion": (_i32, [_vp, _u32, _vp, _u32, _vp]),
     "ptsReprojectMoving": (_i32, [_u32, _u32, _fptr, _vp, C.POINTER(pt_packed_camera), _u32, _u32, _vp,
                                   C.POINTER(pt_packed_camera), _vp, _u32, C.POINTER(pt_reproject_parameters), _fptr]),
+    "ptsRectifyHistory": (_i32, [_u32, _u32, _fptr, _fptr, _vp, C.POINTER(pt_rectify_parameters), _fptr]),
     "ptsCentralCameraRay": (_i32, [C.POINTER(pt_packed_camera), _u32, _u32, _u32, _u32, _fptr, _fptr]),
     "ptsFrameStatistics": (_i32, [_u32, _u32, _fptr, _fptr, C.POINTER(pt_frame_statistics)]),
     "ptsTileStatistics": (_i32, [_u32, _u32, _fptr, _fptr, _f32, _vp]),
@@ -393,6 +407,7 @@ HIP_API = {
     "ptReprojectSampleBufferMoving": (_i32, [_vp, _vp, _vp, C.POINTER(pt_packed_camera), _vp,
                                              C.POINTER(pt_packed_camera), _vp, _u32,
                                              C.POINTER(pt_reproject_parameters), _vp]),
+    "ptRectifyHistory": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(pt_rectify_parameters), _vp]),
     "ptComputeFrameStatistics": (_i32, [_vp, _vp, _vp, C.POINTER(pt_frame_statistics)]),
     "ptComputeTileStatistics": (_i32, [_vp, _vp, _vp, _f32, _vp]),
     "ptSetBasicRendererActiveTiles": (_i32, [_vp, _vp, _vp, _u32]),

@@ -160,6 +160,12 @@ hipError_t pt_launch_reproject(const float4* prev, const float4* prev_guides, ui
                                const pt_packed_camera* prev_camera, const float4* guides, uint32_t w, uint32_t h,
                                const pt_packed_camera* camera, const pt_shape_motion* motion, uint32_t motion_count,
                                const pt_reproject_parameters* p, float4* out, hipStream_t st);
+// History validation (rectify.hip): the history hist
+// held against the windows of the new accumulator cur under the current
+// guides, all w x h -> out.  out may be hist, not cur.  p has passed
+// pt_rectify_parameters_ok.
+hipError_t pt_launch_rectify(const float4* hist, const float4* cur, const float4* guides, uint32_t w, uint32_t h,
+                             const pt_rectify_parameters* p, float4* out, hipStream_t st);
 // dst += src per component.
 hipError_t pt_launch_accumulate(float4* dst, const float4* src, uint64_t n, hipStream_t st);
 // compact: the completion-queue instantiation (ShadeTile), for scenes whose

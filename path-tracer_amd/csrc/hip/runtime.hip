@@ -11,6 +11,7 @@
 #include "../../../include/pt_api.h"
 #include "../../../include/pt_denoise.h"
 #include "../../../include/pt_reproject.h"
+#include "../../../include/pt_rectify.h"
 #include "../../../include/pt_stats.h"
 
 #include <rccl/rccl.h>
@@ -2440,6 +2441,39 @@ int ptReprojectSampleBufferMoving(pt_device* d, pt_sample_buffer* prev, pt_denoi
                                   const pt_reproject_parameters* p, pt_sample_buffer* dst)
 {
     return Reproject(d, prev, pg, pc, g, c, motion, motion_count, p, dst);
+}
+
+// --- history validation (rectify.hip) --------------------------
+
+int ptRectifyHistory(pt_device* d, pt_sample_buffer* history, pt_sample_buffer* current, pt_denoise_guides* g,
+                     const pt_rectify_parameters* p, pt_sample_buffer* dst)
+{
+    if (!d || !history || !current || !g || !p || !dst) { SetError("null argument"); return -1; }
+    if (history == current || dst == current) {
+        SetError("rectify: current is also the history or dst");
+        return -1;
+    }
+    if (history->dev != d || current->dev != d || dst->dev != d || g->dev != d) {
+        SetError("rectify: objects of another device");
+        return -1;
+    }
+    for (const pt_sample_buffer* s : {history, current, dst}) {
+        if (s->width != g->width || s->height != g->height) {
+            SetError("rectify: size mismatch (history %ux%u, current %ux%u, guides %ux%u, dst %ux%u)", history->width,
+                     history->height, current->width, current->height, g->width, g->height, dst->width, dst->height);
+            return -1;
+        }
+    }
+    if (!pt_rectify_parameters_ok(p)) {
+        SetError("rectify: bad parameters (Radius in 1..3, MinNeighbours in 1..49, Sigma finite and >= 0, "
+                 "ClampedHistory > 0, NormalCosine in (-1, 1])");
+        return -1;
+    }
+    PT_HIP(hipSetDevice(d->id));
+    PT_TIMED(d, PT_KERNEL_REPROJECT,
+             pt_launch_rectify(history->accum, current->accum, g->records.ptr, g->width, g->height, p, dst->accum,
+                               d->stream));
+    return 0;
 }
 
 // --- frame statistics (stats.hip) ------------------------------

@@ -606,6 +606,54 @@ def reproject_host(prev_accum: np.ndarray, prev_guides: np.ndarray, prev_camera,
     return out
 
 
+class RectifyParameters:
+    """pt_rectify_parameters (pt_packed.h): the window of new samples a
+    carried history is held against (Radius; MinNeighbours members or the
+    pixel stays untested; NormalCosine between a member's normal and the
+    centre's), the half width of the allowed box in standard deviations
+    (Sigma) and the cap on a clipped pixel's sample count (ClampedHistory;
+    inf: none).  The defaults are the setting tools/exp_rectify.py's rule
+    chose; MinNeighbours 25 is meant for Radius 3's 49
+    pixels: lower it with the radius (a Radius 1 window has 9)."""
+
+    def __init__(self, Radius: int = 3, MinNeighbours: int = 25, Sigma: float = 1.0, ClampedHistory: float = 8.0,
+                 NormalCosine: float = 0.9):
+        self.Radius, self.MinNeighbours = int(Radius), int(MinNeighbours)
+        self.Sigma, self.ClampedHistory, self.NormalCosine = float(Sigma), float(ClampedHistory), float(NormalCosine)
+
+    def as_struct(self) -> N.pt_rectify_parameters:
+        # Out-of-range counts reach the library's check instead of ctypes' wrap-around.
+        return N.pt_rectify_parameters(min(max(self.Radius, 0), 0xFFFFFFFF), min(max(self.MinNeighbours, 0), 0xFFFFFFFF),
+                                       self.Sigma, self.ClampedHistory, self.NormalCosine)
+
+
+def rectify_host(history: np.ndarray, current: np.ndarray, guides: np.ndarray,
+                 params: "RectifyParameters | None" = None) -> np.ndarray:
+    """History validation on the CPU (ptsRectifyHistory, libptscene.so), which
+    the device kernel equals bit for bit.  history: (H, W, 4) accumulator in
+    (mean * n, n) form, e.g. reproject_host's result; current: the (H, W, 4)
+    accumulator of the new rounds alone; guides: the current view's (H, W)
+    DENOISE_GUIDE_DTYPE records.  Returns the (H, W, 4) history with every
+    pixel's mean pulled into the box its window of current samples allows and
+    the count of a pulled pixel cut."""
+    a = np.ascontiguousarray(history, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"history of shape {a.shape}, expected (H, W, 4)")
+    b = np.ascontiguousarray(current, dtype=np.float32)
+    if b.shape != a.shape:
+        raise ValueError(f"current accumulator of shape {b.shape}, history {a.shape}")
+    g = np.ascontiguousarray(guides, dtype=N.DENOISE_GUIDE_DTYPE)
+    if g.shape != a.shape[:2]:
+        raise ValueError(f"guides of shape {g.shape}, accumulator {a.shape[:2]}")
+    out = np.zeros_like(a)
+    p = (params or RectifyParameters()).as_struct()
+    rc = N.scene_lib().ptsRectifyHistory(a.shape[1], a.shape[0], N.fptr(a), N.fptr(b), g.ctypes.data, C.byref(p),
+                                         N.fptr(out))
+    if rc != 0:
+        raise PathTracerError(f"ptsRectifyHistory: bad arguments (status {rc})")
+    return out
+
+
 class DenoiseGuides:
     """Per-pixel primary-hit records of the scene camera's central rays
     (normal, hit time, base colour, shape) that steer the denoiser, plus the
@@ -750,6 +798,22 @@ class SampleBuffer:
             raise
         return dst
 
+    def rectify(self, current: "SampleBuffer", guides: "DenoiseGuides", params: "RectifyParameters | None" = None,
+                out: "SampleBuffer | None" = None) -> "SampleBuffer":
+        """History validation on the device (ptRectifyHistory; enqueues): this
+        buffer is a carried history in (mean * n, n) form, `current` the
+        accumulator of the new rounds alone, `guides` the current view's.
+        `out` (this buffer itself when None: in place) receives the history
+        pulled into the box each pixel's window of current samples allows,
+        with the count of a pulled pixel cut; current.accumulate(out) then
+        gives the frame to go on rendering into.  current and guides are not
+        written."""
+        dst = out if out is not None else self
+        p = (params or RectifyParameters()).as_struct()
+        _check(N.hip_lib().ptRectifyHistory(self.device.handle, self._h, current.handle, guides.handle, C.byref(p),
+                                            dst.handle), "ptRectifyHistory")
+        return dst
+
     def statistics(self, other: "SampleBuffer | None" = None) -> FrameStatistics:
         """Frame statistics on the device (ptComputeFrameStatistics; blocks):
         of this buffer, or, with `other` (an independent render of the same
@@ -807,15 +871,33 @@ class FrameHistory:
     glue over DenoiseGuides.render and SampleBuffer.reproject."""
 
     def __init__(self, device: "Device", width: int, height: int, params: "ReprojectParameters | None" = None,
-                 follow_shapes: bool = False):
+                 follow_shapes: bool = False, validate: "RectifyParameters | bool | None" = None):
         """follow_shapes: also keep the frame's packed shapes and reproject
         with the motion table between the two frames (shape_motion), so that
         a moved object keeps its history.  The scene's entities must be the
-        same from frame to frame."""
+        same from frame to frame.
+        validate: True (default RectifyParameters) or a RectifyParameters:
+        the history is held against the new frame's own samples before it
+        counts, so that shading that changed without
+        any geometry changing loses its weight.  begin_frame() then
+        reprojects into a buffer this object owns and leaves the frame's
+        sample buffer cleared; merge() joins the two after the frame's first
+        run()."""
         self.device = device
         self.width, self.height = int(width), int(height)
         self.params = params
         self.follow_shapes = bool(follow_shapes)
+        if validate is None or validate is False:
+            self.validate = None
+        elif validate is True:
+            self.validate = RectifyParameters()
+        elif isinstance(validate, RectifyParameters):
+            self.validate = validate
+        else:
+            raise ValueError(f"validate: True or a RectifyParameters expected, got {validate!r}")
+        self.held = None           # validate: the reprojected history until merge() (owned)
+        self._unmerged = False      # validate: begin_frame() was called and merge() not yet
+        self._carried = False       # the last begin_frame() carried a history
         self.shapes = None          # the last frame's packed shapes (follow_shapes)
         self._spare = DenoiseGuides(device, self.width, self.height)
         self.guides = None          # the current frame's guides (after begin_frame)
@@ -830,7 +912,11 @@ class FrameHistory:
         the last call's buffer.  True: it now holds the reprojected history;
         False (first call): it was left as it is.  The buffer passed here
         must stay alive until the next call, which reads what the renderer
-        has accumulated in it by then."""
+        has accumulated in it by then.
+        With validate the reprojected history goes into a buffer this object
+        holds and sample_buffer is left as the Reset cleared it; the return
+        value is the same.  Call merge(sample_buffer) after the frame's first
+        run(): a history that is never merged is dropped."""
         if sample_buffer.width != self.width or sample_buffer.height != self.height:
             raise ValueError(f"sample buffer {sample_buffer.width}x{sample_buffer.height}, history "
                              f"{self.width}x{self.height}")
@@ -841,21 +927,47 @@ class FrameHistory:
         shapes = ds.shapes.copy() if self.follow_shapes else None
         if carried:
             motion = shape_motion(self.shapes, shapes) if self.follow_shapes else None
-            self.buffer.reproject(self.guides, self.camera, guides, camera, self.params, out=sample_buffer,
-                                  motion=motion)
+            dst = sample_buffer
+            if self.validate is not None:
+                if self.held is None:
+                    self.held = SampleBuffer(self.device, self.width, self.height)
+                dst = self.held
+            self.buffer.reproject(self.guides, self.camera, guides, camera, self.params, out=dst, motion=motion)
         self.shapes = shapes
         if self.guides is None:
             self._spare = DenoiseGuides(self.device, self.width, self.height)
         else:
             self._spare = self.guides
         self.guides, self.buffer, self.camera = guides, sample_buffer, camera
+        self._carried, self._unmerged = carried, self.validate is not None
         return carried
 
+    def merge(self, sample_buffer: "SampleBuffer"):
+        """With validate, after the frame's first run(k): holds the history
+        begin_frame() reprojected against the k rounds sample_buffer now
+        holds (SampleBuffer.rectify, in place) and adds it to them
+        (sample_buffer.accumulate); both enqueue.  Further run() calls then
+        accumulate on top, and refine_tiles(min_count=...) goes on rendering
+        where the count was cut.  Does nothing on the first frame, which
+        carried nothing.  sample_buffer is begin_frame()'s."""
+        if self.validate is None:
+            raise ValueError("merge: this FrameHistory was created without validate")
+        if not self._unmerged:
+            raise ValueError("merge: no begin_frame() since the last merge()")
+        if sample_buffer is not self.buffer:
+            raise ValueError("merge: not the sample buffer passed to begin_frame()")
+        self._unmerged = False
+        if not self._carried:
+            return
+        self.held.rectify(sample_buffer, self.guides, self.validate)
+        sample_buffer.accumulate(self.held)
+
     def close(self):
-        for g in (self._spare, self.guides):
+        for g in (self._spare, self.guides, self.held):
             if g is not None:
                 g.close()
-        self._spare = self.guides = self.buffer = None
+        self._spare = self.guides = self.buffer = self.held = None
+        self._unmerged = False
 
 
 class BasicRenderer:

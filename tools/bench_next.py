@@ -32,6 +32,12 @@
   one in which every shape is flagged as moved (identity matrices, so the
   same taps), beside ptReprojectSampleBuffer's kernel, ptRenderSampleBuffer
   and one a-trous iteration in the same run; every figure three times.
+* rectify (ptRectifyHistory, rectify.hip): kernel ms of
+  the history validation at Radius 1, 2 and 3 on C3, a history of 8 rounds
+  reprojected after reproject's small pan held against 2 new rounds, beside
+  the reprojection launch, ptRenderSampleBuffer and one a-trous iteration
+  (step 1, 25 global taps) of the same run, at 1920x1080 and 3840x2160; every
+  figure three times.
 * tiles (ptComputeTileStatistics, stats.hip, and ptSetBasicRendererActiveTiles;
   DESIGN.md §6 row 10): kernel ms of the per-tile statistics launch, single
   and pair, beside ptComputeFrameStatistics on the same buffers in the same
@@ -44,7 +50,7 @@
   on all of the job's threads, and the RGB -> spectrum table.
 
 Kernel times are HIP events on the device stream (ptGetKernelStats).
-Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|preview|openpbr|host ...]
+Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|rectify|preview|openpbr|host ...]
 (default: all).
 """
 import json
@@ -450,6 +456,67 @@ def reproject_moving(pt, dev):
     return out
 
 
+def rectify(pt, dev):
+    """Per size, radius{1,2,3}_ms: the validation kernel (out of place, so
+    every call sees the same history; MinNeighbours 1, so that no radius
+    skips its second pass) on a history of 8 rounds reprojected
+    after reproject()'s pan and a Cur of 2 rounds; reproject_ms, resolve_ms,
+    denoise_step1_ms: the yardsticks on the same buffers; radius3_clipped: the
+    share of pixels Radius 3 changes.  Each time is a list: the mean
+    of 10 timed calls after a warm-up call, taken three times in turn."""
+    out = {}
+    scene = pt.Scene.config(3)
+    cam = scene.find_camera(0)
+    ds = pt.DeviceScene(dev)
+    (px, py, pz), (rx, ry, rz) = C3_POSE
+    for W, H in ((1920, 1080), (3840, 2160)):
+        scene.move_camera(cam, position=(px, py, pz), rotation=(rx, ry, rz))
+        scene.pack()
+        ds.update(scene)
+        prev_cam = ds.cameras[0].copy()
+        prev, hist, cur, dst = (pt.SampleBuffer(dev, W, H) for _ in range(4))
+        r = pt.BasicRenderer(dev, ds, prev)
+        r.RenderFlags = 3
+        r.reset()
+        r.run(8)
+        prev_guides, guides = pt.DenoiseGuides(dev, W, H), pt.DenoiseGuides(dev, W, H)
+        prev_guides.render(ds, 0)
+        scene.move_camera(cam, position=(px + 0.02, py + 0.02, pz), rotation=(rx, ry, rz + 0.02))
+        scene.pack()
+        ds.update(scene)
+        now_cam = ds.cameras[0].copy()
+        guides.render(ds, 0)
+        prev.reproject(prev_guides, prev_cam, guides, now_cam, out=hist)
+        rc = pt.BasicRenderer(dev, ds, cur)
+        rc.RenderFlags = 3
+        rc.FrameIndex = 100
+        rc.reset()
+        rc.run(2)
+        runs = {"resolve_ms": (K_RESOLVE, lambda: prev.render(ToneMappingMode=pt.TONE_MAPPING_ACES)),
+                "denoise_step1_ms": (K_DENOISE, lambda: prev.denoise(prev_guides, pt.DenoiseParameters(Iterations=1),
+                                                                     out=dst)),
+                "reproject_ms": (K_REPROJECT, lambda: prev.reproject(prev_guides, prev_cam, guides, now_cam, out=dst))}
+        for radius in (1, 2, 3):
+            p = pt.RectifyParameters(Radius=radius, MinNeighbours=1)   # every pixel with a member runs both passes
+            runs[f"radius{radius}_ms"] = (K_REPROJECT, lambda p=p: hist.rectify(cur, guides, p, out=dst))
+        res = {"pixels": W * H}
+        for key in runs:
+            res[key] = []
+        for _ in range(3):
+            for key, (kernel, fn) in runs.items():
+                fn()   # warm
+                ms, _ = timed(dev, kernel, fn, 10)
+                res[key].append(round(ms, 4))
+        hist.rectify(cur, guides, pt.RectifyParameters(MinNeighbours=1), out=dst)
+        res["radius3_clipped"] = round(float((dst.read() != hist.read()).any(axis=-1).mean()), 4)
+        out[f"{W}x{H}"] = res
+        for x in (guides, prev_guides, rc, r, dst, cur, hist, prev):
+            x.close()
+    ds.close()
+    scene.close()
+    return out
+
+
 def preview(pt, dev):
     out = {}
     modes = {"base_color": pt.PREVIEW_RENDER_MODE_BASE_COLOR, "shaded": pt.PREVIEW_RENDER_MODE_BASE_COLOR_SHADED,
@@ -530,6 +597,7 @@ def host_builds(pt):
 def main():
     pt = load()
     entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "tiles": tiles, "reproject": reproject, "reproject_moving": reproject_moving,
+               "rectify": rectify,
                "preview": preview, "openpbr": openpbr}
     want = sys.argv[1:] or list(entries) + ["host"]
     dev = pt.Device(0)

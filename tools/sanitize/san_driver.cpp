@@ -33,6 +33,11 @@
 //                               model that project inside, far outside, behind
 //                               and to non-finite positions, with random,
 //                               empty and NaN / inf histories; rejected arguments
+//   san_driver rectify          ptsRectifyHistory on random, all-empty and NaN /
+//                               inf / denormal images from 1x1 to 67x45, every
+//                               Radius, MinNeighbours 1 and 49, Sigma 0,
+//                               ClampedHistory +inf, in place and out of
+//                               place; rejected arguments
 #include "../../path-tracer_amd/csrc/scene/scene.hpp"
 #include "../../path-tracer_amd/csrc/scene/configs.hpp"
 #include "../../path-tracer_amd/csrc/scene/image.hpp"
@@ -573,9 +578,98 @@ static int ReprojectMoving()
     return bad != 0;
 }
 
+// ptsRectifyHistory: the images lie in arrays of exactly
+// 4 * W * H floats and W * H guide records, so a window tap past an edge is
+// ASan's.  A count is only ever cut; in place equals out of place.
+static int Rectify()
+{
+    std::mt19937 rng(17);
+    std::uniform_real_distribution<float> u(0.0f, 4.0f);
+    const float nan = std::nanf(""), inf = HUGE_VALF;
+    const float odd[] = {0.0f, -0.0f, -1.0f, nan, inf, -inf, 1e-45f, 1e-38f, 3e38f, 1.0f, 4294967296.0f, 2.3283064e-10f};
+    const uint32_t sizes[][2] = {{1, 1}, {1, 7}, {3, 2}, {5, 3}, {15, 15}, {16, 16}, {17, 16}, {16, 17}, {33, 18}, {67, 45}};
+    const pt_rectify_parameters sets[] = {{1, 1, 1.0f, 8.0f, 0.9f}, {2, 6, 0.0f, 8.0f, 0.9f}, {3, 9, 1.0f, inf, 0.9f},
+                                          {3, 49, 1.0f, 8.0f, 1.0f}, {2, 1, 2.5f, 0.5f, -0.999f}};
+    int bad = 0;
+    for (auto& wh : sizes) {
+        const uint32_t W = wh[0], H = wh[1];
+        const size_t n = (size_t)W * H;
+        // kind 0: random; 1: all empty; 2: every component drawn from the odd values (NaN, inf, denormals ...)
+        for (int kind = 0; kind < 3; kind++) {
+            std::vector<float> hist(4 * n), cur(4 * n);
+            std::vector<pt_denoise_guide> g(n);
+            for (std::vector<float>* v : {&hist, &cur}) {
+                for (size_t i = 0; i < 4 * n; i++) {
+                    if (kind == 0) (*v)[i] = i % 4 == 3 ? (float)(rng() % 70) : u(rng);
+                    else if (kind == 1) (*v)[i] = 0.0f;
+                    else (*v)[i] = odd[rng() % (sizeof(odd) / sizeof(odd[0]))];
+                }
+            }
+            for (size_t i = 0; i < n; i++) {
+                const uint32_t pick = rng() % 8;
+                g[i].shape = pick == 0 ? PT_SHAPE_INDEX_NONE : pick % 3;
+                for (int k = 0; k < 3; k++)
+                    g[i].normal[k] = kind == 2 ? odd[rng() % (sizeof(odd) / sizeof(odd[0]))] : (k == 2 ? 1.0f : 0.01f * (float)(rng() % 60));
+                g[i].time = 1.0f;
+                g[i].albedo[0] = g[i].albedo[1] = g[i].albedo[2] = 0.5f;
+            }
+            for (const pt_rectify_parameters& p : sets) {
+                std::vector<float> out(4 * n, -7.0f), in_place(hist);
+                if (ptsRectifyHistory(W, H, hist.data(), cur.data(), g.data(), &p, out.data()) != 0 ||
+                    ptsRectifyHistory(W, H, in_place.data(), cur.data(), g.data(), &p, in_place.data()) != 0) {
+                    std::printf("rectify: failed\n");
+                    return 1;
+                }
+                bad += std::memcmp(out.data(), in_place.data(), 4 * n * sizeof(float)) != 0;
+                size_t kept = 0, cut = 0, none = 0;
+                for (size_t i = 0; i < n; i++) {
+                    const float* h = &hist[4 * i];
+                    const float* o = &out[4 * i];
+                    const bool usable = std::isfinite(h[0]) && std::isfinite(h[1]) && std::isfinite(h[2]) &&
+                                        std::isfinite(h[3]) && h[3] > 0.0f;
+                    if (!usable) { none++; bad += o[0] != 0.0f || o[1] != 0.0f || o[2] != 0.0f || o[3] != 0.0f; continue; }
+                    if (std::memcmp(h, o, 4 * sizeof(float)) == 0) { kept++; continue; }
+                    cut++;
+                    bad += !(o[3] <= h[3] && o[3] <= p.ClampedHistory && o[3] > 0.0f);
+                }
+                std::printf("rectify %ux%u kind %d radius %u min %u sigma %g clamp %g: kept %zu cut %zu none %zu\n", W, H, kind,
+                            p.Radius, p.MinNeighbours, (double)p.Sigma, (double)p.ClampedHistory, kept, cut, none);
+            }
+        }
+    }
+    // rejected arguments leave `out` untouched
+    float hist[4] = {1, 1, 1, 1}, cur[4] = {1, 2, 1, 1}, out[4], before[4];
+    std::memset(out, 0x55, sizeof(out));
+    std::memcpy(before, out, sizeof(out));
+    pt_denoise_guide g;
+    std::memset(&g, 0, sizeof(g));
+    const pt_rectify_parameters ok = {3, 9, 1.0f, 8.0f, 0.9f};
+    bad += ptsRectifyHistory(1, 1, nullptr, cur, &g, &ok, out) == 0;
+    bad += ptsRectifyHistory(1, 1, hist, nullptr, &g, &ok, out) == 0;
+    bad += ptsRectifyHistory(1, 1, hist, cur, nullptr, &ok, out) == 0;
+    bad += ptsRectifyHistory(1, 1, hist, cur, &g, nullptr, out) == 0;
+    bad += ptsRectifyHistory(1, 1, hist, cur, &g, &ok, nullptr) == 0;
+    bad += ptsRectifyHistory(0, 1, hist, cur, &g, &ok, out) == 0;
+    bad += ptsRectifyHistory(1, 0, hist, cur, &g, &ok, out) == 0;
+    bad += ptsRectifyHistory(1, 1, cur, cur, &g, &ok, out) == 0;
+    const pt_rectify_parameters wrong[] = {{0, 9, 1.0f, 8.0f, 0.9f}, {4, 9, 1.0f, 8.0f, 0.9f}, {3, 0, 1.0f, 8.0f, 0.9f},
+                                           {3, 50, 1.0f, 8.0f, 0.9f}, {3, 9, -1.0f, 8.0f, 0.9f}, {3, 9, inf, 8.0f, 0.9f},
+                                           {3, 9, nan, 8.0f, 0.9f}, {3, 9, 1.0f, 0.0f, 0.9f}, {3, 9, 1.0f, nan, 0.9f},
+                                           {3, 9, 1.0f, 8.0f, -1.0f}, {3, 9, 1.0f, 8.0f, 1.5f}, {3, 9, 1.0f, 8.0f, nan}};
+    for (const pt_rectify_parameters& p : wrong) bad += ptsRectifyHistory(1, 1, hist, cur, &g, &p, out) == 0;
+    bad += std::memcmp(out, before, sizeof(out)) != 0;
+    bad += ptsRectifyHistory(1, 1, hist, cur, &g, &ok, cur) == 0;          // out is current
+    bad += cur[1] != 2.0f;
+    const pt_rectify_parameters one = {1, 1, 0.0f, 8.0f, 0.9f};
+    g.normal[2] = 1.0f;                                                    // the centre is its own window
+    bad += ptsRectifyHistory(1, 1, hist, cur, &g, &one, out) != 0 || out[0] != 1.0f || out[1] != 2.0f || out[3] != 1.0f;
+    std::printf("rectify: %d checks wrong\n", bad);
+    return bad != 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise|stats|tile_stats|reproject|reproject_moving ...\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise|stats|tile_stats|reproject|reproject_moving|rectify ...\n"); return 2; }
     std::string cmd = argv[1];
     if (cmd == "decode") return Decode(argc - 2, argv + 2);
     if (cmd == "model") return Model(argc - 2, argv + 2);
@@ -587,6 +681,7 @@ int main(int argc, char** argv)
     if (cmd == "tile_stats") return TileStats();
     if (cmd == "reproject") return Reproject();
     if (cmd == "reproject_moving") return ReprojectMoving();
+    if (cmd == "rectify") return Rectify();
     std::fprintf(stderr, "unknown command %s\n", cmd.c_str());
     return 2;
 }
