@@ -190,6 +190,19 @@ enum {
 };
 int       ptSetSceneStackFormat(pt_scene* scene, uint32_t format);
 int       ptSetSceneHitRecordForm(pt_scene* scene, uint32_t form);
+/* The extend kernel's form (no effect on results).  AUTO: a scene that is one
+ * mesh instance (one shape, the TLAS root a leaf) is traced by a mesh-only
+ * traversal loop, every other scene by the general two-level one; GENERAL
+ * forces the latter (tests, A/B timing).  Set takes effect at the next
+ * ptUpdateScene; Get reports the form the uploaded scene runs (GENERAL or
+ * MESH). */
+enum {
+    PT_EXTEND_FORM_AUTO    = 0,
+    PT_EXTEND_FORM_GENERAL = 1,
+    PT_EXTEND_FORM_MESH    = 2,
+};
+int       ptSetSceneExtendForm(pt_scene* scene, uint32_t form);
+int       ptGetSceneExtendForm(pt_scene* scene, uint32_t* form);
 /* Traversal stack entries the uploaded scene can need (TLAS depth + deepest
  * BLAS depth, each capped at the reference's Stack[32]); the extend kernel keeps
  * 20 in LDS and spills the rest to a per-ray global buffer. */

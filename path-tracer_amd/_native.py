@@ -351,6 +351,8 @@ HIP_API = {
     "ptUpdateScene": (_i32, [_vp, _vp, C.POINTER(pt_scene_packs), _u32]),
     "ptSetSceneStackFormat": (_i32, [_vp, _u32]),
     "ptSetSceneHitRecordForm": (_i32, [_vp, _u32]),
+    "ptSetSceneExtendForm": (_i32, [_vp, _u32]),
+    "ptGetSceneExtendForm": (_i32, [_vp, C.POINTER(C.c_uint32)]),
     "ptDestroyScene": (None, [_vp, _vp]),
     "ptCreateSampleBuffer": (_vp, [_vp, _u32, _u32]),
     "ptDestroySampleBuffer": (None, [_vp, _vp]),

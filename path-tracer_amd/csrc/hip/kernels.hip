@@ -1128,7 +1128,12 @@ constexpr bool kRendererSource = std::is_same<Src, ray_source_slots>::value;
 // One ray: Trace() by LaneStep to completion, the compact hit stored, and
 // the ray's ShadeOrder outcome class ballotted (positions outside the image:
 // class 0, shade skips them).
-template <bool SPILL, int CAP, class E, class Src>
+//
+// MESH (a dscene::single_mesh scene): the mesh-only loop instead, one pass
+// for the lanes whose ray takes the exact fast division and one for the
+// others (usually none); each lane's ray is traced as before, only beside
+// other lanes.
+template <bool SPILL, int CAP, class E, bool MESH = false, class Src>
 PT_DEV void ExtendRay(const dscene& S, const Src& src, tstack<SPILL, CAP, E>& st, uint32_t slot)
 {
     pt3 O, V;
@@ -1136,10 +1141,20 @@ PT_DEV void ExtendRay(const dscene& S, const Src& src, tstack<SPILL, CAP, E>& st
     uint32_t cls = 0;
     if (src.load(slot, O, V, D)) {
         lane_state Ln;
-        LaneBegin(S, Ln, O, V, D);
-        no_stats ns;
-        if (S.g.ShapeCount != 0) {
-            while (!LaneStep<SPILL, CAP, Src, no_stats, true, E>(S, Ln, st, src, slot, ns)) {}
+        if constexpr (MESH) {
+            MeshBegin(S, Ln, O, V, D);
+            if (Ln.exact) {
+                while (!MeshStep<true>(S, Ln, st)) {}
+            } else {
+                while (!MeshStep<false>(S, Ln, st)) {}
+            }
+            if (Ln.Shape == 0xFFFFFFFEu) Ln.Shape = 0;
+        } else {
+            LaneBegin(S, Ln, O, V, D);
+            no_stats ns;
+            if (S.g.ShapeCount != 0) {
+                while (!LaneStep<SPILL, CAP, Src, no_stats, true, E>(S, Ln, st, src, slot, ns)) {}
+            }
         }
         src.store(slot, Ln, S.vidx21 != 0);
         if (Ln.Shape == SHAPE_INDEX_NONE) {
@@ -1155,7 +1170,7 @@ PT_DEV void ExtendRay(const dscene& S, const Src& src, tstack<SPILL, CAP, E>& st
 }
 
 // One tile of extend: thread i traces the ray at position tile*256 + i.
-template <class Src, bool SPILL, int CAP, class E>
+template <class Src, bool SPILL, int CAP, class E, bool MESH = false>
 PT_DEV void ExtendTile(const dscene& S, const Src& src, uint32_t n, uint32_t* spill, uint32_t spill_stride, E* smem,
                        uint32_t tile, bool timed, const float4* nc = nullptr, uint32_t ncn = 0)
 {
@@ -1168,7 +1183,7 @@ PT_DEV void ExtendTile(const dscene& S, const Src& src, uint32_t n, uint32_t* sp
     st.stride = spill_stride;
     st.nc = nc;
     st.ncn = ncn;
-    ExtendRay<SPILL, CAP, E>(S, src, st, slot);
+    ExtendRay<SPILL, CAP, E, MESH>(S, src, st, slot);
     if constexpr (kRendererSource<Src>) {
         if (timed && (threadIdx.x & 63u) == 0)
             src.L.tilecost[tile * 4 + (threadIdx.x >> 6)] = (uint32_t)(__builtin_amdgcn_s_memtime() - t0);
@@ -1186,9 +1201,14 @@ PT_DEV uint32_t NodeCacheFill(const dscene& S, float4* nc)
     return nodes;
 }
 
-template <class Src, bool SPILL, int MINW, int CAP, class E = uint32_t, bool NC = false>
-__global__ __launch_bounds__(256, MINW) void extend_kernel(dscene S, Src src, uint32_t n, uint32_t* spill,
-                                                                  uint32_t spill_stride)
+// (The mesh-only instantiations without the node cache declare 8 waves per
+// SIMD: left at MINW the compiler gave them 75-78 VGPRs, 6 waves, where 58-63
+// hold the loop without a spill; C3 extend on the two 32-bit stack formats
+// 0.3142-0.3149 -> 0.3036-0.3038 and 0.3313-0.3328 -> 0.3228-0.3243 ms.  The
+// one with the cache takes 56 either way.)
+template <class Src, bool SPILL, int MINW, int CAP, class E = uint32_t, bool NC = false, bool MESH = false>
+__global__ __launch_bounds__(256, (MESH && !NC) ? 8 : MINW) void extend_kernel(dscene S, Src src, uint32_t n,
+                                                                               uint32_t* spill, uint32_t spill_stride)
 {
     __shared__ E smem[CAP * 256];
     __shared__ float4 ncache[NC ? 4 * PT_NODE_CACHE_PAIRS : 1];
@@ -1207,7 +1227,7 @@ __global__ __launch_bounds__(256, MINW) void extend_kernel(dscene S, Src src, ui
             timed = true;
         }
     }
-    ExtendTile<Src, SPILL, CAP, E>(S, src, n, spill, spill_stride, smem, tile, timed, ncache, ncn);
+    ExtendTile<Src, SPILL, CAP, E, MESH>(S, src, n, spill, spill_stride, smem, tile, timed, ncache, ncn);
 }
 
 // Longest-first dispatch order for the next extend: tiles by their slowest
@@ -1966,7 +1986,10 @@ hipError_t pt_launch_raygen(const ptd::dscene& S, const ptd::dslots& L, const pt
 
 uint32_t pt_extend_stack_cap() { return PT_EXTEND_CAP; }
 
-template <class Src, class E>
+// MESH: the mesh-only instantiation (dscene::single_mesh scenes; every
+// variant below has one).  The statistics, preview and fused round kernels
+// stay on the general LaneStep.
+template <class Src, class E, bool MESH>
 static void LaunchExtendE(const ptd::dscene& S, const Src& src, uint32_t n, uint32_t blocks, uint32_t* spill,
                           hipStream_t st)
 {
@@ -1974,17 +1997,25 @@ static void LaunchExtendE(const ptd::dscene& S, const Src& src, uint32_t n, uint
     // stack's 20 KB it would cost occupancy).
     if constexpr (sizeof(E) == 2) {
         if (!spill && S.node_cache) {
-            hipLaunchKernelGGL((ptd::extend_kernel<Src, false, PT_EXTEND_MINW, PT_EXTEND_CAP, E, true>), dim3(blocks),
-                               dim3(256), 0, st, S, src, n, spill, n);
+            hipLaunchKernelGGL((ptd::extend_kernel<Src, false, PT_EXTEND_MINW, PT_EXTEND_CAP, E, true, MESH>),
+                               dim3(blocks), dim3(256), 0, st, S, src, n, spill, n);
             return;
         }
     }
     if (spill)
-        hipLaunchKernelGGL((ptd::extend_kernel<Src, true, PT_EXTEND_MINW, PT_EXTEND_CAP, E>), dim3(blocks), dim3(256),
-                           0, st, S, src, n, spill, n);
-    else
-        hipLaunchKernelGGL((ptd::extend_kernel<Src, false, PT_EXTEND_MINW, PT_EXTEND_CAP, E>), dim3(blocks),
+        hipLaunchKernelGGL((ptd::extend_kernel<Src, true, PT_EXTEND_MINW, PT_EXTEND_CAP, E, false, MESH>), dim3(blocks),
                            dim3(256), 0, st, S, src, n, spill, n);
+    else
+        hipLaunchKernelGGL((ptd::extend_kernel<Src, false, PT_EXTEND_MINW, PT_EXTEND_CAP, E, false, MESH>), dim3(blocks),
+                           dim3(256), 0, st, S, src, n, spill, n);
+}
+
+template <class Src, class E>
+static void LaunchExtendE(const ptd::dscene& S, const Src& src, uint32_t n, uint32_t blocks, uint32_t* spill,
+                          hipStream_t st)
+{
+    if (S.single_mesh) LaunchExtendE<Src, E, true>(S, src, n, blocks, spill, st);
+    else LaunchExtendE<Src, E, false>(S, src, n, blocks, spill, st);
 }
 
 // n: rays (the spill stride and the bound of the ray index); blocks: the

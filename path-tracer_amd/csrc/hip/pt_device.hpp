@@ -50,6 +50,14 @@ struct dscene {
     float sky_flat;                // SampleParametricSpectrum((0, 0, 100), L) for any finite L (SkyFlat)
     uint32_t node_cache;           // BLAS nodes [0, node_cache) are the top child pairs the extend kernel
                                    // keeps in LDS (NodeCacheLayout, runtime.hip); 0: no cache
+    // One-mesh scenes (ShapeCount == 1, the TLAS root a leaf, shape 0 a mesh
+    // instance; classified at upload, runtime.hip): extend runs the mesh-only
+    // loop (traverse.hpp MeshStep) and reads what its prologue needs of the
+    // shape and of the mesh root from these kernel arguments (scalar loads)
+    // instead of through three dependent per-lane loads.
+    uint32_t single_mesh;
+    uint32_t mesh_root[2];         // the mesh root node's index words {FaceBeginOrNodeIndex, FaceEndIndex}
+    float mesh_from[16];           // shape 0's Transform.From
 };
 
 // LDS node cache of the extend kernel: this many BLAS child pairs (64 B

@@ -155,6 +155,8 @@ struct pt_scene {
     uint32_t cached_pairs = 0;   // BLAS child pairs at the front of the device node array (NodeCacheLayout)
     bool blas_packable = false;  // BlasWordsPackable / BlasWords16FirstBits of the device node layout
     uint32_t blas16_bits = 0;
+    uint32_t extend_form = PT_EXTEND_FORM_AUTO;     // ptSetSceneExtendForm (applied at the next update)
+    bool one_mesh = false;       // the uploaded scene is one mesh instance (OneMeshScene; d.mesh_root, d.mesh_from)
     bool valid = false;
 };
 
@@ -624,6 +626,29 @@ int ptSetSceneHitRecordForm(pt_scene* s, uint32_t form)
     return 0;
 }
 
+int ptSetSceneExtendForm(pt_scene* s, uint32_t form)
+{
+    if (!s || form > PT_EXTEND_FORM_GENERAL) { SetError("ptSetSceneExtendForm: bad argument"); return -1; }
+    s->extend_form = form;
+    return 0;
+}
+
+int ptGetSceneExtendForm(pt_scene* s, uint32_t* form)
+{
+    if (!s || !form) { SetError("null argument"); return -1; }
+    *form = (s->valid && s->d.single_mesh) ? PT_EXTEND_FORM_MESH : PT_EXTEND_FORM_GENERAL;
+    return 0;
+}
+
+// A scene whose Trace() is one mesh traversal (dscene::single_mesh): one
+// shape, the TLAS root a leaf that names it, and that shape a mesh instance.
+static bool OneMeshScene(const pt_scene_packs* p)
+{
+    return p->globals->ShapeCount == 1 && p->shape_count == 1 && p->shape_node_count >= 1 &&
+           p->shape_nodes[0].ChildNodeIndices == 0 && p->shape_nodes[0].ShapeIndex == 0 &&
+           p->shapes[0].Type == PT_SHAPE_TYPE_MESH_INSTANCE;
+}
+
 // UpdateVulkanScene (scene.cpp:1692-2006): synchronous upload of the packs.
 // Box-coordinate condition of the extend kernel's exact fast slab division
 // (pt_device.hpp, IntersectBoundingBox): every TLAS / BLAS bound is 0 or has
@@ -857,6 +882,17 @@ int ptUpdateScene(pt_device* d, pt_scene* s, const pt_scene_packs* p, uint32_t d
         }
         PT_HIP(s->shapes.upload(sh.data(), sh.size()));
         PT_HIP(s->mesh_nodes.upload(nodes.data(), nodes.size()));
+        // One-mesh scenes: what the mesh-only extend loop's prologue reads of
+        // the shape and of the mesh root (device node layout) rides in the
+        // kernel arguments.  A property of the uploaded scene, so it follows
+        // every upload that touches shapes or meshes.
+        s->one_mesh = OneMeshScene(p) && sh[0].MeshRootNodeIndex < nodes.size();
+        if (s->one_mesh) {
+            const pt_packed_mesh_node& root = nodes[sh[0].MeshRootNodeIndex];
+            s->d.mesh_root[0] = root.FaceBeginOrNodeIndex;
+            s->d.mesh_root[1] = root.FaceEndIndex;
+            std::memcpy(s->d.mesh_from, sh[0].Transform.From, sizeof s->d.mesh_from);
+        }
     }
     if (first || (dirty & PT_SCENE_DIRTY_MESHES)) {
         // Device face records carry {Position0, Edge1, Edge2} (traverse.hpp
@@ -932,6 +968,9 @@ int ptUpdateScene(pt_device* d, pt_scene* s, const pt_scene_packs* p, uint32_t d
     }
     // The LDS node cache rides with the u16 stack (kernels.hip LaunchExtendE).
     D.node_cache = D.stack16 ? 2 * s->cached_pairs : 0u;
+    // Extend's form: the mesh-only loop for a one-mesh scene, unless
+    // ptSetSceneExtendForm asks for the general one (identical results).
+    D.single_mesh = (s->one_mesh && s->extend_form == PT_EXTEND_FORM_AUTO) ? 1u : 0u;
     s->camera_count = p->camera_count;
     s->stack_needed = need;
     s->valid = true;

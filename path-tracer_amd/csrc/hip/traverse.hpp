@@ -555,6 +555,88 @@ PT_DEV bool LaneStep(const dscene& S, lane_state& L, tstack<SPILL, CAP, SE>& st,
     return TlasStep(S, L, st, src, slot, ss);
 }
 
+// --- one-mesh scenes (dscene::single_mesh) ----------------------------------
+//
+// The scene is one mesh instance under a leaf TLAS root, so a ray's Trace()
+// is: transform into the mesh's space, IntersectMeshNode, done.  The lane has
+// one level, one stack and one `exact` flag for its whole traversal; none of
+// LaneStep's TLAS half can change the result.  MeshBegin is LaneBegin plus
+// the first (TLAS leaf) step, from kernel arguments; MeshStep is LaneStep's
+// FACE_STEP BLAS half, operation for operation, with `exact` a template
+// parameter, the stack indexed by dB alone and the lane complete at "not
+// moved and the stack empty".  Hit.ShapeIndex stays 0xFFFFFFFE on a face hit;
+// the caller sets it to shape 0 after its loop (TlasStep's BLAS exit).
+
+PT_DEV void MeshBegin(const dscene& S, lane_state& L, pt3 O, pt3 V, float Duration)
+{
+    L.Time = Duration;
+    L.Shape = SHAPE_INDEX_NONE;
+    L.Prim = 0;
+    L.C = v3s(0);
+    L.HA = 0;
+    L.HB = 0;
+    L.dT = 0;
+    L.dB = 0;
+    L.blas = 0;
+    SetLevelRay(S, L, mat4_mul_point(S.mesh_from, O), mat4_mul_vector(S.mesh_from, V));
+    L.na = S.mesh_root[0];
+    L.nb = S.mesh_root[1];
+}
+
+template <bool EXACT, bool SPILL, int CAP, class SE>
+PT_DEV bool MeshStep(const dscene& S, lane_state& L, tstack<SPILL, CAP, SE>& st)
+{
+    // (See LaneStep for why the divergent halves compute fresh values only
+    // and every state update is a select after the join.)
+    const bool face = L.nb > 0;
+    bool fmiss = true;
+    float fT, fU, fW, TA, TB;
+    uint32_t aw0, aw1, bw0, bw1, fVA, fVB;
+    uint32_t pair = L.na;
+    asm("" : "=v"(fT), "=v"(fU), "=v"(fW), "=v"(TA), "=v"(TB), "=v"(fVA), "=v"(fVB));
+    asm("" : "=v"(aw0), "=v"(aw1), "=v"(bw0), "=v"(bw1));
+    if (face) {
+        fmiss = FaceTest(S, L.na, L, L.na < L.nb, fT, fU, fW, fVA, fVB);
+    } else {
+        float4 a0, a1, b0, b1;
+        if (L.na < st.ncn) {
+            const PT_LDS f32x4* Cp = (const PT_LDS f32x4*)st.nc + 2 * L.na;
+            a0 = F4(Cp[0]); a1 = F4(Cp[1]); b0 = F4(Cp[2]); b1 = F4(Cp[3]);
+        } else {
+            const PT_GLOBAL f32x4* Np = (const PT_GLOBAL f32x4*)S.mesh_nodes + 2 * (size_t)L.na;
+            a0 = F4(Np[0]); a1 = F4(Np[1]); b0 = F4(Np[2]); b1 = F4(Np[3]);
+        }
+        IntersectBoxPair(L.O, L.V, L.Y, L.Time, a0, a1, b0, b1, EXACT, TA, TB);
+        aw0 = __float_as_uint(a0.w), aw1 = __float_as_uint(a1.w);
+        bw0 = __float_as_uint(b0.w), bw1 = __float_as_uint(b1.w);
+    }
+    L.Time = fmiss ? L.Time : fT;
+    L.Shape = fmiss ? L.Shape : 0xFFFFFFFEu;
+    L.Prim = fmiss ? L.Prim : L.na;
+    L.HA = fmiss ? L.HA : fVA;
+    L.HB = fmiss ? L.HB : fVB;
+    L.C = v3(fmiss ? L.C.x : 1 - fU - fW, fmiss ? L.C.y : fU, fmiss ? L.C.z : fW);
+    bool goB = TA > TB;
+    float Tfar = goB ? TA : TB;
+    bool push = !face & (Tfar < PT_INFINITY);
+    bool moved = (face & (L.na + 1 < L.nb)) | (!face & (goB | (TA < PT_INFINITY)));
+    if (push & (L.dB < 32)) {
+        st.put(L.dB++, BlasPush<SE>(S, goB ? aw0 : bw0, goB ? aw1 : bw1, pair + (goB ? 0u : 1u)));
+    }
+    uint32_t na = face ? L.na + 1 : (goB ? bw0 : aw0);
+    uint32_t nb = face ? L.nb : (goB ? bw1 : aw1);
+    // The lane's end is mask logic beside the pop, not an exit inside the
+    // `!moved` branch: with the exit nested there the compiler split the loop
+    // in two and the lanes that need a pop waited until no lane of the wave
+    // was still moving.
+    const bool pop = !moved & (L.dB > 0);
+    const bool done = !moved & (L.dB == 0);
+    if (pop) BlasPop<SE>(S, st.get(--L.dB), na, nb);
+    L.na = na;
+    L.nb = nb;
+    return done;
+}
+
 // The compact hit record extend stores for shade: {Time, Shape, z, w} and
 // {C.y, C.z}.  In a vidx21 scene z, w are a mesh face's packed vertex indices
 // and C.x = 1 - C.y - C.z is re-evaluated by the reader (the face test's own

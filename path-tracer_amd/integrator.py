@@ -118,6 +118,17 @@ class DeviceScene:
         """PT_HIT_RECORD_* (0 auto, 1 face index); next update()."""
         _check(N.hip_lib().ptSetSceneHitRecordForm(self._h, int(form)), "ptSetSceneHitRecordForm")
 
+    def set_extend_form(self, form: int):
+        """PT_EXTEND_FORM_* (0 auto, 1 general traversal loop); next update()."""
+        _check(N.hip_lib().ptSetSceneExtendForm(self._h, int(form)), "ptSetSceneExtendForm")
+
+    @property
+    def extend_form(self) -> int:
+        """The extend form the uploaded scene runs: 1 general, 2 mesh-only (ptGetSceneExtendForm)."""
+        v = C.c_uint32(0)
+        _check(N.hip_lib().ptGetSceneExtendForm(self._h, C.byref(v)), "ptGetSceneExtendForm")
+        return int(v.value)
+
     def update(self, scene, dirty_flags: int = 0xFFFFFFFF):
         packs = scene.packs() if hasattr(scene, "packs") else scene
         _check(N.hip_lib().ptUpdateScene(self.device.handle, self._h, C.byref(packs), dirty_flags), "ptUpdateScene")
