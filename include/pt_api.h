@@ -108,7 +108,7 @@ enum {
     PT_KERNEL_PREVIEW = 4,
     PT_KERNEL_ROUND   = 5,   /* fused extend + shade of a small partition (one launch per round) */
     PT_KERNEL_ROUNDS  = 6,   /* a round batch: several rounds of every tile in one launch */
-    PT_KERNEL_DENOISE = 7,   /* one a-trous iteration of ptDenoiseSampleBuffer */
+    PT_KERNEL_DENOISE = 7,   /* one a-trous iteration of ptDenoiseSampleBuffer; ptDespikeSampleBuffer's launch */
     PT_KERNEL_GUIDES  = 8,   /* ptRenderDenoiseGuides */
     PT_KERNEL_STATS   = 9,   /* ptComputeFrameStatistics' and ptComputeTileStatistics' passes, ptAccumulateSampleBuffer's add */
     PT_KERNEL_REPROJECT = 10, /* ptReprojectSampleBuffer, ptReprojectSampleBufferMoving, ptRectifyHistory */
@@ -483,6 +483,27 @@ int  ptSetDenoiseVariant(pt_denoise_guides* guides, uint32_t variant);
  * device, when Iterations > 8 or when a sigma is not > 0. */
 int  ptDenoiseSampleBufferPair(pt_device* device, pt_sample_buffer* a, pt_sample_buffer* b, pt_denoise_guides* guides,
                                const pt_denoise_pair_parameters* params, pt_sample_buffer* dst);
+/* Firefly clamp in front of the denoisers (no reference counterpart;
+ * definition, kernel design and measured times in DESIGN.md §6 row 12;
+ * arithmetic in pt_despike.h).  src is an accumulator, guides the records of
+ * the same view.  A pixel's value is the largest component of its mean
+ * colour; where it exceeds Scale times the Rank-th largest value among the
+ * pixels of the window around it that show the same surface, plus Floor, the
+ * pixel's colour sums are scaled down onto that limit.  Every pixel of dst
+ * receives src's pixel, clamped or bit for bit; the sample count is never
+ * changed, and a pixel that is not usable (a non-finite component, a count
+ * not > 0) or has fewer than MinNeighbours such neighbours keeps its bits.
+ * dst stays an accumulator: denoise it, add it to another, or go on
+ * rendering into it.  For two half renders call it once per half.  Enqueues
+ * one launch (counted under PT_KERNEL_DENOISE) and returns, like
+ * ptRectifyHistory.  src and guides are not written; two calls on the same
+ * inputs give the same bits, and the result equals ptsDespike's (pt_scene.h)
+ * bit for bit.  Fails, launching and writing nothing, on a NULL argument,
+ * dst == src (a window reads neighbours another block would have replaced),
+ * an object of another device, objects of different sizes, or a parameter
+ * outside its range (pt_packed.h). */
+int  ptDespikeSampleBuffer(pt_device* device, pt_sample_buffer* src, pt_denoise_guides* guides,
+                           const pt_despike_parameters* params, pt_sample_buffer* dst);
 
 /* Temporal reprojection (no reference counterpart; definition, kernel design
  * and measured times in DESIGN.md §6 row 8; arithmetic in pt_reproject.h):

@@ -243,6 +243,18 @@ typedef struct pt_rectify_parameters {
     float    NormalCosine;             /* in (-1, 1], default 0.9: smallest dot product with a member's normal */
 } pt_rectify_parameters;
 
+/* Firefly clamp (arithmetic in pt_despike.h): the window
+ * of neighbours a pixel's brightest colour component is held against, which
+ * of their values is the yardstick and how far above it a pixel may lie. */
+typedef struct pt_despike_parameters {
+    uint32_t Radius;                   /* 1..3, default 3: the window is (2 Radius + 1)^2 pixels */
+    uint32_t Rank;                     /* 1..4, default 3: the yardstick is the Rank-th largest neighbour */
+    uint32_t MinNeighbours;            /* Rank..(2 Radius + 1)^2 - 1, default 8: fewer members leave the pixel untested */
+    float    Scale;                    /* finite, >= 0, default 1: the limit is Scale * yardstick + Floor */
+    float    Floor;                    /* finite, >= 0 and not -0, default 0: nothing at or below it is clamped */
+    float    NormalCosine;             /* in (-1, 1], default 0.9: smallest dot product with a member's normal */
+} pt_despike_parameters;
+
 /* One shape's motion between two packed scenes, filled
  * by ptsShapeMotion (pt_scene.h) and read by the moving-shape reprojection
  * (pt_reproject.h).  Point: rows 0..2 of the affine map from the current
@@ -307,6 +319,7 @@ static_assert(sizeof(pt_denoise_parameters) == 20, "denoise_parameters");
 static_assert(sizeof(pt_denoise_pair_parameters) == 20, "denoise_pair_parameters");
 static_assert(sizeof(pt_reproject_parameters) == 16, "reproject_parameters");
 static_assert(sizeof(pt_rectify_parameters) == 20, "rectify_parameters");
+static_assert(sizeof(pt_despike_parameters) == 24, "despike_parameters");
 static_assert(sizeof(pt_shape_motion) == 96, "shape_motion");
 static_assert(sizeof(pt_packed_transform) == 128, "packed_transform");
 static_assert(sizeof(pt_packed_texture) == 32, "packed_texture");

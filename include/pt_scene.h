@@ -250,6 +250,19 @@ int  ptsReprojectMoving(uint32_t prev_width, uint32_t prev_height, const float* 
  * parameter outside its range (pt_packed.h).  Single-threaded. */
 int  ptsRectifyHistory(uint32_t width, uint32_t height, const float* history, const float* current,
                        const pt_denoise_guide* guides, const pt_rectify_parameters* params, float* out_rgba);
+/* The firefly clamp on the host (no reference counterpart; definition in
+ * DESIGN.md §6 row 12, arithmetic in pt_despike.h): the CPU path and the
+ * implementation ptDespikeSampleBuffer (pt_api.h) is compared with, bit for
+ * bit.  accum: an accumulator (XYZ sums + sample count); guides: the same
+ * view's records; both width x height.  out_rgba receives accum with the
+ * colour sums of every pixel whose value (the largest component of its mean
+ * colour) exceeds Scale * (the Rank-th largest value among the window's
+ * pixels of the same surface) + Floor scaled onto that limit; every other
+ * pixel, and every sample count, keeps its bits.  Returns non-zero, leaving
+ * out_rgba untouched, on a NULL argument, an empty image, out_rgba == accum or
+ * a parameter outside its range (pt_packed.h).  Single-threaded. */
+int  ptsDespike(uint32_t width, uint32_t height, const float* accum, const pt_denoise_guide* guides,
+                const pt_despike_parameters* params, float* out_rgba);
 /* pt_reproject.h's central camera ray of pixel (x, y) of a width x height
  * frame (the guide kernel's ray: pixel centre, lens centre, the velocity
  * after its packed round trip).  Non-zero on a NULL argument, an empty frame

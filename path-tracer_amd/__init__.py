@@ -19,7 +19,8 @@ from .integrator import (Device, DeviceScene, SampleBuffer, BasicRenderer, Comm,
                          DenoiseParameters, DenoiseGuides, denoise_host, FrameStatistics, frame_statistics_host,
                          render_until_noise, DenoisePairParameters, denoise_pair_host, ReprojectParameters,
                          reproject_host, FrameHistory, shape_motion, tile_statistics_host, tile_mask_of_region,
-                         refine_tiles, REFINE_MIN_ROUNDS, RectifyParameters, rectify_host)
+                         refine_tiles, REFINE_MIN_ROUNDS, RectifyParameters, rectify_host, DespikeParameters,
+                         despike_host)
 from ._native import (PREVIEW_RENDER_MODE_BASE_COLOR, PREVIEW_RENDER_MODE_BASE_COLOR_SHADED, PREVIEW_RENDER_MODE_NORMAL,
                       PREVIEW_RENDER_MODE_MATERIAL_INDEX, PREVIEW_RENDER_MODE_PRIMITIVE_INDEX,
                       PREVIEW_RENDER_MODE_MESH_COMPLEXITY, PREVIEW_RENDER_MODE_SCENE_COMPLEXITY)

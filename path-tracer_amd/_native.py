@@ -122,6 +122,21 @@ class pt_rectify_parameters(C.Structure):
 
 assert C.sizeof(pt_rectify_parameters) == 20
 
+
+class pt_despike_parameters(C.Structure):
+    """pt_despike_parameters (include/pt_packed.h)."""
+    _fields_ = [
+        ("Radius", C.c_uint32),
+        ("Rank", C.c_uint32),
+        ("MinNeighbours", C.c_uint32),
+        ("Scale", C.c_float),
+        ("Floor", C.c_float),
+        ("NormalCosine", C.c_float),
+    ]
+
+
+assert C.sizeof(pt_despike_parameters) == 24
+
 STATS_BINS = 256
 
 
@@ -252,7 +267,7 @@ KERNEL_PREVIEW = 4
 KERNEL_ROUND = 5     # fused extend + shade (partitions that fit the GPU at once)
 KERNEL_ROUNDS = 6    # a round batch: several rounds of every tile in one launch (PT_KERNEL_ROUNDS)
 MAX_SPLIT = 4        # PT_MAX_SPLIT: tile groups of ptSetBasicRendererSplit
-KERNEL_DENOISE = 7   # one a-trous iteration (PT_KERNEL_DENOISE)
+KERNEL_DENOISE = 7   # one a-trous iteration; ptDespikeSampleBuffer's launch (PT_KERNEL_DENOISE)
 KERNEL_GUIDES = 8    # ptRenderDenoiseGuides (PT_KERNEL_GUIDES)
 DENOISE_MAX_ITERATIONS = 8
 DENOISE_VARIANT_AUTO, DENOISE_VARIANT_GATHER, DENOISE_VARIANT_LATTICE = 0, 1, 2
@@ -330,6 +345,7 @@ SCENE_API = {
     "ptsReprojectMoving": (_i32, [_u32, _u32, _fptr, _vp, C.POINTER(pt_packed_camera), _u32, _u32, _vp,
                                   C.POINTER(pt_packed_camera), _vp, _u32, C.POINTER(pt_reproject_parameters), _fptr]),
     "ptsRectifyHistory": (_i32, [_u32, _u32, _fptr, _fptr, _vp, C.POINTER(pt_rectify_parameters), _fptr]),
+    "ptsDespike": (_i32, [_u32, _u32, _fptr, _vp, C.POINTER(pt_despike_parameters), _fptr]),
     "ptsCentralCameraRay": (_i32, [C.POINTER(pt_packed_camera), _u32, _u32, _u32, _u32, _fptr, _fptr]),
     "ptsFrameStatistics": (_i32, [_u32, _u32, _fptr, _fptr, C.POINTER(pt_frame_statistics)]),
     "ptsTileStatistics": (_i32, [_u32, _u32, _fptr, _fptr, _f32, _vp]),
@@ -410,6 +426,7 @@ HIP_API = {
                                              C.POINTER(pt_packed_camera), _vp, _u32,
                                              C.POINTER(pt_reproject_parameters), _vp]),
     "ptRectifyHistory": (_i32, [_vp, _vp, _vp, _vp, C.POINTER(pt_rectify_parameters), _vp]),
+    "ptDespikeSampleBuffer": (_i32, [_vp, _vp, _vp, C.POINTER(pt_despike_parameters), _vp]),
     "ptComputeFrameStatistics": (_i32, [_vp, _vp, _vp, C.POINTER(pt_frame_statistics)]),
     "ptComputeTileStatistics": (_i32, [_vp, _vp, _vp, _f32, _vp]),
     "ptSetBasicRendererActiveTiles": (_i32, [_vp, _vp, _vp, _u32]),

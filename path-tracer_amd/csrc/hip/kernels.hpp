@@ -166,6 +166,11 @@ hipError_t pt_launch_reproject(const float4* prev, const float4* prev_guides, ui
 // pt_rectify_parameters_ok.
 hipError_t pt_launch_rectify(const float4* hist, const float4* cur, const float4* guides, uint32_t w, uint32_t h,
                              const pt_rectify_parameters* p, float4* out, hipStream_t st);
+// Firefly clamp (despike.hip): the accumulator src under
+// its view's guides, both w x h -> out.  out is not src.  p has passed
+// pt_despike_parameters_ok.
+hipError_t pt_launch_despike(const float4* src, const float4* guides, uint32_t w, uint32_t h,
+                             const pt_despike_parameters* p, float4* out, hipStream_t st);
 // dst += src per component.
 hipError_t pt_launch_accumulate(float4* dst, const float4* src, uint64_t n, hipStream_t st);
 // compact: the completion-queue instantiation (ShadeTile), for scenes whose

@@ -12,6 +12,7 @@
 #include "../../../include/pt_denoise.h"
 #include "../../../include/pt_reproject.h"
 #include "../../../include/pt_rectify.h"
+#include "../../../include/pt_despike.h"
 #include "../../../include/pt_stats.h"
 
 #include <rccl/rccl.h>
@@ -2512,6 +2513,38 @@ int ptRectifyHistory(pt_device* d, pt_sample_buffer* history, pt_sample_buffer* 
     PT_TIMED(d, PT_KERNEL_REPROJECT,
              pt_launch_rectify(history->accum, current->accum, g->records.ptr, g->width, g->height, p, dst->accum,
                                d->stream));
+    return 0;
+}
+
+// --- firefly clamp (despike.hip) -------------------------------
+
+int ptDespikeSampleBuffer(pt_device* d, pt_sample_buffer* src, pt_denoise_guides* g, const pt_despike_parameters* p,
+                          pt_sample_buffer* dst)
+{
+    if (!d || !src || !g || !p || !dst) { SetError("null argument"); return -1; }
+    if (dst == src) {
+        SetError("despike: dst is src");
+        return -1;
+    }
+    if (src->dev != d || dst->dev != d || g->dev != d) {
+        SetError("despike: objects of another device");
+        return -1;
+    }
+    for (const pt_sample_buffer* s : {src, dst}) {
+        if (s->width != g->width || s->height != g->height) {
+            SetError("despike: size mismatch (src %ux%u, guides %ux%u, dst %ux%u)", src->width, src->height, g->width,
+                     g->height, dst->width, dst->height);
+            return -1;
+        }
+    }
+    if (!pt_despike_parameters_ok(p)) {
+        SetError("despike: bad parameters (Radius in 1..3, Rank in 1..4, MinNeighbours in Rank..(2 Radius + 1)^2 - 1, "
+                 "Scale and Floor finite and >= 0, Floor not -0, NormalCosine in (-1, 1])");
+        return -1;
+    }
+    PT_HIP(hipSetDevice(d->id));
+    PT_TIMED(d, PT_KERNEL_DENOISE,
+             pt_launch_despike(src->accum, g->records.ptr, g->width, g->height, p, dst->accum, d->stream));
     return 0;
 }
 

@@ -665,6 +665,51 @@ def rectify_host(history: np.ndarray, current: np.ndarray, guides: np.ndarray,
     return out
 
 
+class DespikeParameters:
+    """pt_despike_parameters (pt_packed.h): the firefly clamp's window
+    (Radius; MinNeighbours members or the pixel stays untested; NormalCosine
+    between a member's normal and the centre's), which neighbour is the
+    yardstick (the Rank-th largest value, so that Rank - 1 fireflies in a
+    window do not raise it) and the limit Scale * yardstick + Floor above
+    which a pixel is scaled down.  The defaults are the setting
+    tools/exp_despike.py's rule chose: Scale 1 clamps
+    every pixel above its window's third brightest neighbour, 7 to 8 % of a
+    frame, and removes 1 to 20 % of a noisy frame's energy; Scale 2 touches
+    fireflies only.  MinNeighbours 8 suits every radius (a Radius 1 window
+    has 8 neighbours)."""
+
+    def __init__(self, Radius: int = 3, Rank: int = 3, MinNeighbours: int = 8, Scale: float = 1.0, Floor: float = 0.0,
+                 NormalCosine: float = 0.9):
+        self.Radius, self.Rank, self.MinNeighbours = int(Radius), int(Rank), int(MinNeighbours)
+        self.Scale, self.Floor, self.NormalCosine = float(Scale), float(Floor), float(NormalCosine)
+
+    def as_struct(self) -> N.pt_despike_parameters:
+        # Out-of-range counts reach the library's check instead of ctypes' wrap-around.
+        u = [min(max(v, 0), 0xFFFFFFFF) for v in (self.Radius, self.Rank, self.MinNeighbours)]
+        return N.pt_despike_parameters(u[0], u[1], u[2], self.Scale, self.Floor, self.NormalCosine)
+
+
+def despike_host(accum: np.ndarray, guides: np.ndarray, params: "DespikeParameters | None" = None) -> np.ndarray:
+    """The firefly clamp on the CPU (ptsDespike, libptscene.so), which the
+    device kernel equals bit for bit.  accum: (H, W, 4) XYZ sums + sample
+    count; guides: the same view's (H, W) DENOISE_GUIDE_DTYPE records.
+    Returns the (H, W, 4) accumulator with the colour sums of every pixel that
+    stands out of its window scaled down onto the window's limit; every other
+    pixel and every count keeps its bits."""
+    a = np.ascontiguousarray(accum, dtype=np.float32)
+    if a.ndim != 3 or a.shape[2] != 4:
+        raise ValueError(f"accumulator of shape {a.shape}, expected (H, W, 4)")
+    g = np.ascontiguousarray(guides, dtype=N.DENOISE_GUIDE_DTYPE)
+    if g.shape != a.shape[:2]:
+        raise ValueError(f"guides of shape {g.shape}, accumulator {a.shape[:2]}")
+    out = np.zeros_like(a)
+    p = (params or DespikeParameters()).as_struct()
+    rc = N.scene_lib().ptsDespike(a.shape[1], a.shape[0], N.fptr(a), g.ctypes.data, C.byref(p), N.fptr(out))
+    if rc != 0:
+        raise PathTracerError(f"ptsDespike: bad arguments (status {rc})")
+    return out
+
+
 class DenoiseGuides:
     """Per-pixel primary-hit records of the scene camera's central rays
     (normal, hit time, base colour, shape) that steer the denoiser, plus the
@@ -770,6 +815,27 @@ class SampleBuffer:
         try:
             _check(N.hip_lib().ptDenoiseSampleBufferPair(self.device.handle, self._h, other.handle, guides.handle,
                                                          C.byref(p), dst.handle), "ptDenoiseSampleBufferPair")
+        except PathTracerError:
+            if out is None:
+                dst.close()
+            raise
+        return dst
+
+    def despike(self, guides: "DenoiseGuides", params: "DespikeParameters | None" = None,
+                out: "SampleBuffer | None" = None) -> "SampleBuffer":
+        """The firefly clamp on the device (ptDespikeSampleBuffer; enqueues):
+        `out` (a new sample buffer of this size when None; never this buffer)
+        receives this accumulator with the pixels that stand out of their
+        window scaled down onto the window's limit, counts unchanged, so that
+        out.denoise(...), out.denoise_pair(...), other.accumulate(out) and
+        rectify work on it as on any accumulator.  One call per buffer: for
+        two halves, a.despike(g) and b.despike(g) before denoise_pair.  This
+        buffer and the guides are not written."""
+        dst = out if out is not None else SampleBuffer(self.device, self.width, self.height)
+        p = (params or DespikeParameters()).as_struct()
+        try:
+            _check(N.hip_lib().ptDespikeSampleBuffer(self.device.handle, self._h, guides.handle, C.byref(p),
+                                                     dst.handle), "ptDespikeSampleBuffer")
         except PathTracerError:
             if out is None:
                 dst.close()

@@ -38,6 +38,11 @@
   the reprojection launch, ptRenderSampleBuffer and one a-trous iteration
   (step 1, 25 global taps) of the same run, at 1920x1080 and 3840x2160; every
   figure three times.
+* despike (ptDespikeSampleBuffer, despike.hip): kernel ms
+  of the firefly clamp at Radius 1, 2 and 3 on 8 rounds of C3, beside
+  ptRectifyHistory at the same radii (the same frame as its own history,
+  held against 2 new rounds), ptRenderSampleBuffer and one a-trous iteration
+  of the same run, at 1920x1080 and 3840x2160; every figure three times.
 * tiles (ptComputeTileStatistics, stats.hip, and ptSetBasicRendererActiveTiles;
   DESIGN.md §6 row 10): kernel ms of the per-tile statistics launch, single
   and pair, beside ptComputeFrameStatistics on the same buffers in the same
@@ -50,7 +55,7 @@
   on all of the job's threads, and the RGB -> spectrum table.
 
 Kernel times are HIP events on the device stream (ptGetKernelStats).
-Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|rectify|preview|openpbr|host ...]
+Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|rectify|despike|preview|openpbr|host ...]
 (default: all).
 """
 import json
@@ -517,6 +522,60 @@ def rectify(pt, dev):
     return out
 
 
+def despike(pt, dev):
+    """Per size, radius{1,2,3}_ms: the clamp (the other parameters at their
+    defaults) on 8 rounds of C3; rectify_radius{1,2,3}_ms: the history validation
+    (MinNeighbours 1, as in rectify()) of that frame reprojected onto its own
+    view against 2 new rounds; resolve_ms, denoise_step1_ms: the yardsticks on
+    the same buffers; radius3_clamped: the share of pixels Radius 3 changes.
+    Each time is a list: the mean of 10 timed calls after a warm-up call,
+    taken three times in turn."""
+    out = {}
+    scene = pt.Scene.config(3)
+    scene.pack()
+    ds = pt.DeviceScene(dev)
+    ds.update(scene)
+    cam = ds.cameras[0].copy()
+    for W, H in ((1920, 1080), (3840, 2160)):
+        src, hist, cur, dst = (pt.SampleBuffer(dev, W, H) for _ in range(4))
+        r = pt.BasicRenderer(dev, ds, src)
+        r.RenderFlags = 3
+        r.reset()
+        r.run(8)
+        guides, prev_guides = pt.DenoiseGuides(dev, W, H), pt.DenoiseGuides(dev, W, H)
+        guides.render(ds, 0)
+        prev_guides.render(ds, 0)
+        src.reproject(prev_guides, cam, guides, cam, out=hist)
+        rc = pt.BasicRenderer(dev, ds, cur)
+        rc.RenderFlags = 3
+        rc.FrameIndex = 100
+        rc.reset()
+        rc.run(2)
+        runs = {"resolve_ms": (K_RESOLVE, lambda: src.render(ToneMappingMode=pt.TONE_MAPPING_ACES)),
+                "denoise_step1_ms": (K_DENOISE, lambda: src.denoise(guides, pt.DenoiseParameters(Iterations=1), out=dst))}
+        for radius in (1, 2, 3):
+            p = pt.DespikeParameters(Radius=radius)
+            runs[f"radius{radius}_ms"] = (K_DENOISE, lambda p=p: src.despike(guides, p, out=dst))
+            q = pt.RectifyParameters(Radius=radius, MinNeighbours=1)
+            runs[f"rectify_radius{radius}_ms"] = (K_REPROJECT, lambda q=q: hist.rectify(cur, guides, q, out=dst))
+        res = {"pixels": W * H}
+        for key in runs:
+            res[key] = []
+        for _ in range(3):
+            for key, (kernel, fn) in runs.items():
+                fn()   # warm
+                ms, _ = timed(dev, kernel, fn, 10)
+                res[key].append(round(ms, 4))
+        src.despike(guides, pt.DespikeParameters(), out=dst)
+        res["radius3_clamped"] = round(float((dst.read() != src.read()).any(axis=-1).mean()), 4)
+        out[f"{W}x{H}"] = res
+        for x in (prev_guides, guides, rc, r, dst, cur, hist, src):
+            x.close()
+    ds.close()
+    scene.close()
+    return out
+
+
 def preview(pt, dev):
     out = {}
     modes = {"base_color": pt.PREVIEW_RENDER_MODE_BASE_COLOR, "shaded": pt.PREVIEW_RENDER_MODE_BASE_COLOR_SHADED,
@@ -597,7 +656,7 @@ def host_builds(pt):
 def main():
     pt = load()
     entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "tiles": tiles, "reproject": reproject, "reproject_moving": reproject_moving,
-               "rectify": rectify,
+               "rectify": rectify, "despike": despike,
                "preview": preview, "openpbr": openpbr}
     want = sys.argv[1:] or list(entries) + ["host"]
     dev = pt.Device(0)
