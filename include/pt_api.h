@@ -442,6 +442,30 @@ int         ptReadPreviewAOVs(pt_device* device, pt_preview* context, pt_preview
 pt_denoise_guides* ptCreateDenoiseGuides(pt_device* device, uint32_t width, uint32_t height);
 void ptDestroyDenoiseGuides(pt_device* device, pt_denoise_guides* guides);
 int  ptRenderDenoiseGuides(pt_device* device, pt_scene* scene, pt_denoise_guides* guides, uint32_t camera_index);
+/* Guides that follow perfect mirrors and smooth glass to the surface a pixel
+ * shows (the arithmetic is include/pt_guides.h's).  The
+ * ray starts as ptRenderDenoiseGuides' does.  A hit on a basic metal or basic
+ * translucent material whose roughness at the hit is < 1e-3 (the integrator's
+ * HasDirac) is followed, at most max_bounces times: the ray is reflected, or
+ * refracted by the material's base index (glass always transmits; total
+ * internal reflection reflects), and restarted as basic_scatter restarts a
+ * path.  The record is that of the first hit that is not followed: its
+ * normal and base colour, time = the summed hit times of the chain, and
+ * shape = tag << 16 | shape index, where tag is 1 + the index of the first
+ * followed shape (0: seen directly), so that a surface seen directly, in one
+ * mirror and in another are three surfaces to every consumer's equality
+ * test.  A miss writes the miss record with the sky's colour along the last
+ * direction and no tag.  max_bounces = 0 gives ptRenderDenoiseGuides' bits.
+ * Known limits: no Fresnel reflection branch and no dispersion; no
+ * active-shape stack (nested dielectrics are walked surface by surface);
+ * media neither absorb nor scatter the ray; time is a path length, so
+ * reprojection reconstructs the virtual image (exact for planar mirrors);
+ * ptReprojectSampleBufferMoving gives tagged pixels no history (their shape
+ * word is beyond the motion table).  Fails like ptRenderDenoiseGuides, and on
+ * max_bounces > PT_GUIDE_MAX_BOUNCES, launching nothing. */
+#define PT_GUIDE_MAX_BOUNCES 8
+int  ptRenderDenoiseGuidesSpecular(pt_device* device, pt_scene* scene, pt_denoise_guides* guides,
+                                   uint32_t camera_index, uint32_t max_bounces);
 int  ptReadDenoiseGuides(pt_device* device, pt_denoise_guides* guides, pt_denoise_guide* out);
 int  ptWriteDenoiseGuides(pt_device* device, pt_denoise_guides* guides, const pt_denoise_guide* in);
 /* Enqueues the filter: dst's accumulator := the denoised mean XYZ of src in

@@ -28,7 +28,7 @@ from ._native import TONE_MAPPING_CLAMP, TONE_MAPPING_REINHARD, TONE_MAPPING_HAB
 from ._native import (SHADE_DIFFUSE, SHADE_METAL, SHADE_TRANSLUCENT, SHADE_SCATTER, SHADE_OPENPBR, SHADE_PRIMS,
                       SHADE_SKY, SHADE_TEXWRAP)
 from ._native import (DENOISE_GUIDE_DTYPE, DENOISE_MAX_ITERATIONS, DENOISE_VARIANT_AUTO, DENOISE_VARIANT_GATHER,
-                      DENOISE_VARIANT_LATTICE, KERNEL_DENOISE, KERNEL_GUIDES)
+                      DENOISE_VARIANT_LATTICE, GUIDE_MAX_BOUNCES, KERNEL_DENOISE, KERNEL_GUIDES)
 from ._native import KERNEL_STATS, STATS_BINS, STATS_VARIANT_AUTO, STATS_VARIANT_PLAIN, STATS_VARIANT_UNIFORM
 from ._native import KERNEL_REPROJECT, CAMERA_DTYPE, TILE_SIZE, TILE_STATS_DTYPE
 from ._native import SHAPE_DTYPE, SHAPE_MOTION_DTYPE, SHAPE_MOTION_MOVED, SHAPE_MOTION_NO_HISTORY

@@ -269,6 +269,7 @@ KERNEL_ROUNDS = 6    # a round batch: several rounds of every tile in one launch
 MAX_SPLIT = 4        # PT_MAX_SPLIT: tile groups of ptSetBasicRendererSplit
 KERNEL_DENOISE = 7   # one a-trous iteration; ptDespikeSampleBuffer's launch (PT_KERNEL_DENOISE)
 KERNEL_GUIDES = 8    # ptRenderDenoiseGuides (PT_KERNEL_GUIDES)
+GUIDE_MAX_BOUNCES = 8  # ptRenderDenoiseGuidesSpecular (PT_GUIDE_MAX_BOUNCES)
 DENOISE_MAX_ITERATIONS = 8
 DENOISE_VARIANT_AUTO, DENOISE_VARIANT_GATHER, DENOISE_VARIANT_LATTICE = 0, 1, 2
 KERNEL_STATS = 9     # the frame and tile statistics passes and the sample-buffer add (PT_KERNEL_STATS)
@@ -415,6 +416,7 @@ HIP_API = {
     "ptCreateDenoiseGuides": (_vp, [_vp, _u32, _u32]),
     "ptDestroyDenoiseGuides": (None, [_vp, _vp]),
     "ptRenderDenoiseGuides": (_i32, [_vp, _vp, _vp, _u32]),
+    "ptRenderDenoiseGuidesSpecular": (_i32, [_vp, _vp, _vp, _u32, _u32]),
     "ptReadDenoiseGuides": (_i32, [_vp, _vp, _vp]),
     "ptWriteDenoiseGuides": (_i32, [_vp, _vp, _vp]),
     "ptDenoiseSampleBuffer": (_i32, [_vp, _vp, _vp, C.POINTER(pt_denoise_parameters), _vp]),

@@ -24,12 +24,14 @@
 // {colour, luminance variance}, behind one prepare launch that forms the
 // combined frame of two half renders and its prefiltered variance).  The
 // policy is resolved at compile time; the loops exist once.
+#include <type_traits>
 #include "pt_device.hpp"
 #include "traverse.hpp"
 #include "kernels.hpp"
 #include "base_color.hpp"
 #include "../../../include/pt_denoise.h"
 #include "../../../include/pt_reproject.h"
+#include "../../../include/pt_guides.h"
 
 namespace ptd {
 
@@ -63,9 +65,88 @@ struct ray_source_guides {
     }
 };
 
-// A guide record as two float4: {normal, time}, {albedo, shape bits}.
+// The launch record of the SPECULAR instantiation; the
+// plain one keeps guide_args.
+struct guide_args_specular : guide_args {
+    uint32_t max_bounces;
+};
+
+// A bounced lane's world ray, kept in its registers: what TlasStep restores
+// when the lane leaves a BLAS (ray_source_guides::load would hand it the
+// camera ray again).
+struct ray_source_lane {
+    pt3 O, V;
+    PT_DEV bool load(uint32_t, pt3& WO, pt3& WV, float& D) const
+    {
+        WO = O;
+        WV = V;
+        D = PT_HIT_TIME_LIMIT;
+        return true;
+    }
+};
+
+PT_DEV void StoreGuideMiss(const dscene& S, const observe_table& Tb, bool known, pt3 V, float4* __restrict__ rec)
+{
+    pt3 A = v3s(0);
+    if (known) A = XYZToSRGB(ObserveUnderD65(Tb, SampleSkyboxSpectrum(S, V)));
+    rec[0] = make_float4(0, 0, 0, 0);
+    rec[1] = make_float4(A.x, A.y, A.z, __uint_as_float(0xFFFFFFFFu));
+}
+
+// The chain of include/pt_guides.h for one pixel: up to max_bounces + 1 traces
+// through the same LaneBegin / LaneStep, each from an empty stack (LaneBegin
+// zeroes both depths; an entry is always put before it is read, spill rows
+// included).  A lane whose chain ended leaves the loop and waits for the
+// wave's longest chain.
 template <int CAP>
-__global__ __launch_bounds__(256) void guides_kernel(dscene S, guide_args P, uint32_t* spill, uint32_t spill_stride,
+PT_DEV void GuideChain(const dscene& S, const observe_table& Tb, tstack<true, CAP>& st, uint32_t i, bool known, pt3 O,
+                       pt3 V, uint32_t max_bounces, float4* __restrict__ rec)
+{
+    const bool trace = known && S.g.ShapeCount != 0;
+    float total = 0.0f;
+    uint32_t tag = 0;
+    for (uint32_t b = 0; b <= PT_GUIDE_MAX_BOUNCES; b++) {
+        lane_state Ln;
+        LaneBegin(S, Ln, O, V, PT_HIT_TIME_LIMIT);
+        const ray_source_lane cur{O, V};
+        complexity_stats cx;
+        if (trace)
+            while (!LaneStep<true, CAP>(S, Ln, st, cur, i, cx)) {}
+        if (Ln.Shape == SHAPE_INDEX_NONE) {
+            StoreGuideMiss(S, Tb, known, V, rec);
+            return;
+        }
+        float4 h = CompactHit(Ln, S.vidx21 != 0);
+        float2 c = make_float2(Ln.C.y, Ln.C.z);
+        uint32_t Material;
+        pt3 N, TX;
+        pt2 UV;
+        HitAttributesRecord(S, Ln.Shape, h, c, Material, N, TX, UV);
+        const pt3 Nq = UnpackUnitVector(PackUnitVector(N));
+        total = pt_guide_total(total, h.x, b);
+        const uint32_t Type = MUint(S, Material, 0);
+        float Roughness = 1.0f;
+        if (pt_guide_candidate(Type)) Roughness = MaterialTexturableValue(S, Material, pt_guide_roughness_word(Type), UV);
+        if (!pt_guide_followed(Type, Roughness, b, max_bounces)) {
+            pt3 A = XYZToSRGB(MaterialBaseColor(S, Tb, Material, UV));
+            rec[0] = make_float4(Nq.x, Nq.y, Nq.z, total);
+            rec[1] = make_float4(A.x, A.y, A.z, __uint_as_float(pt_guide_shape_word(tag, Ln.Shape)));
+            return;
+        }
+        tag = pt_guide_tag(tag, Ln.Shape);
+        const pt3 TXq = UnpackUnitVector(PackUnitVector(TX));
+        const pt3 W = pt_guide_direction(Type, MFloat(S, Material, PT_BASIC_TRANSLUCENT_IOR), Nq, TXq, V);
+        pt_guide_restart(&O, &V, h.x, W);
+    }
+}
+
+// A guide record as two float4: {normal, time}, {albedo, shape bits}.
+// SPECULAR: the chain through mirrors and smooth glass (GuideChain); the plain
+// instantiation holds no trace of it.
+template <int CAP, bool SPECULAR = false>
+__global__ __launch_bounds__(256) void guides_kernel(dscene S,
+                                                     std::conditional_t<SPECULAR, guide_args_specular, guide_args> P,
+                                                     uint32_t* spill, uint32_t spill_stride,
                                                      float4* __restrict__ out,
                                                      const observe_table* __restrict__ observe)
 {
@@ -83,6 +164,10 @@ __global__ __launch_bounds__(256) void guides_kernel(dscene S, guide_args P, uin
     pt3 O, V;
     float D;
     const bool known = src.load(i, O, V, D);
+    if constexpr (SPECULAR) {
+        GuideChain<CAP>(S, Tb, st, i, known, O, V, P.max_bounces, out + 2 * ((size_t)y * P.w + x));
+        return;
+    }
     lane_state Ln;
     LaneBegin(S, Ln, O, V, D);
     complexity_stats cx;
@@ -458,6 +543,24 @@ hipError_t pt_launch_denoise_guides(const ptd::dscene& S, uint32_t camera_index,
     uint32_t tiles = P.tiles_x * ((h + 15) / 16);
     if (tiles == 0) return hipSuccess;
     hipLaunchKernelGGL(ptd::guides_kernel<20>, dim3(tiles), dim3(256), 0, st, S, P, spill, tiles * 256, guides,
+                       reinterpret_cast<const ptd::observe_table*>(observe_table));
+    return hipGetLastError();
+}
+
+hipError_t pt_launch_denoise_guides_specular(const ptd::dscene& S, uint32_t camera_index, uint32_t max_bounces,
+                                             uint32_t w, uint32_t h, uint32_t* spill, float4* guides,
+                                             const float* observe_table, hipStream_t st)
+{
+    if (max_bounces > PT_GUIDE_MAX_BOUNCES) return hipErrorInvalidValue;
+    ptd::guide_args_specular P;
+    P.camera = camera_index;
+    P.w = w;
+    P.h = h;
+    P.tiles_x = (w + 15) / 16;
+    P.max_bounces = max_bounces;
+    uint32_t tiles = P.tiles_x * ((h + 15) / 16);
+    if (tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL((ptd::guides_kernel<20, true>), dim3(tiles), dim3(256), 0, st, S, P, spill, tiles * 256, guides,
                        reinterpret_cast<const ptd::observe_table*>(observe_table));
     return hipGetLastError();
 }

@@ -115,6 +115,12 @@ hipError_t pt_launch_resolve(const float4* accum, uint32_t n, float brightness, 
 // pt_denoise_guide); spill as for the preview (pt_guides_stack_cap).
 hipError_t pt_launch_denoise_guides(const ptd::dscene& S, uint32_t camera_index, uint32_t w, uint32_t h,
                                     uint32_t* spill, float4* guides, const float* observe_table, hipStream_t st);
+// The guides that follow mirrors and smooth glass (DESIGN.md §6 row 13;
+// include/pt_guides.h): the same launch shape and spill rows, a chain of up to
+// max_bounces + 1 traces per pixel.  max_bounces <= PT_GUIDE_MAX_BOUNCES.
+hipError_t pt_launch_denoise_guides_specular(const ptd::dscene& S, uint32_t camera_index, uint32_t max_bounces,
+                                             uint32_t w, uint32_t h, uint32_t* spill, float4* guides,
+                                             const float* observe_table, hipStream_t st);
 uint32_t pt_guides_stack_cap();
 // One a-trous iteration (step 2^iteration) in -> out.  accumulator: `in` is
 // a sample buffer's accumulator (iteration 0), else a filtered image.

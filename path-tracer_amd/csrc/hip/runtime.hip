@@ -13,6 +13,7 @@
 #include "../../../include/pt_reproject.h"
 #include "../../../include/pt_rectify.h"
 #include "../../../include/pt_despike.h"
+#include "../../../include/pt_guides.h"
 #include "../../../include/pt_stats.h"
 
 #include <rccl/rccl.h>
@@ -2275,9 +2276,18 @@ void ptDestroyDenoiseGuides(pt_device* d, pt_denoise_guides* g)
     delete g;
 }
 
-int ptRenderDenoiseGuides(pt_device* d, pt_scene* s, pt_denoise_guides* g, uint32_t camera_index)
+// specular: ptRenderDenoiseGuidesSpecular's launch.  A chain of zero bounces,
+// and any chain in a scene none of whose shapes has a metal or translucent
+// material (pt_scene::mats: nothing can be followed), is the plain kernel's
+// record bit for bit, so those take the plain kernel.
+static int RenderGuides(pt_device* d, pt_scene* s, pt_denoise_guides* g, uint32_t camera_index, bool specular,
+                        uint32_t max_bounces)
 {
     if (!d || !s || !g) { SetError("null argument"); return -1; }
+    if (specular && max_bounces > PT_GUIDE_MAX_BOUNCES) {
+        SetError("denoise guides: %u bounces, at most %u", max_bounces, (uint32_t)PT_GUIDE_MAX_BOUNCES);
+        return -1;
+    }
     if (s->dev != d || g->dev != d) { SetError("denoise guides: scene or guides belong to another device"); return -1; }
     if (!s->valid) { SetError("denoise guides: scene has no valid packs (call ptUpdateScene)"); return -1; }
     if (camera_index >= s->camera_count) {
@@ -2292,10 +2302,27 @@ int ptRenderDenoiseGuides(pt_device* d, pt_scene* s, pt_denoise_guides* g, uint3
         PT_HIP(g->spill.alloc((need - cap) * threads));
         spill = g->spill.ptr;
     }
+    if (specular && max_bounces != 0 && (s->mats & (PT_MATS_METAL | PT_MATS_TRANSLUCENT)) != 0) {
+        PT_TIMED(d, PT_KERNEL_GUIDES,
+                 pt_launch_denoise_guides_specular(s->d, camera_index, max_bounces, g->width, g->height, spill,
+                                                   g->records.ptr, g->observe.ptr, d->stream));
+        return 0;
+    }
     PT_TIMED(d, PT_KERNEL_GUIDES,
              pt_launch_denoise_guides(s->d, camera_index, g->width, g->height, spill, g->records.ptr, g->observe.ptr,
                                       d->stream));
     return 0;
+}
+
+int ptRenderDenoiseGuides(pt_device* d, pt_scene* s, pt_denoise_guides* g, uint32_t camera_index)
+{
+    return RenderGuides(d, s, g, camera_index, false, 0);
+}
+
+int ptRenderDenoiseGuidesSpecular(pt_device* d, pt_scene* s, pt_denoise_guides* g, uint32_t camera_index,
+                                  uint32_t max_bounces)
+{
+    return RenderGuides(d, s, g, camera_index, true, max_bounces);
 }
 
 int ptReadDenoiseGuides(pt_device* d, pt_denoise_guides* g, pt_denoise_guide* out)

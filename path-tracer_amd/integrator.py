@@ -727,10 +727,20 @@ class DenoiseGuides:
     def handle(self):
         return self._h
 
-    def render(self, scene: "DeviceScene", camera_index: int = 0):
-        """One central camera ray per pixel of packed camera `camera_index` (enqueues)."""
-        _check(N.hip_lib().ptRenderDenoiseGuides(self.device.handle, scene.handle, self._h, int(camera_index)),
-               "ptRenderDenoiseGuides")
+    def render(self, scene: "DeviceScene", camera_index: int = 0, specular_bounces: int = 0):
+        """One central camera ray per pixel of packed camera `camera_index` (enqueues).
+        specular_bounces (up to GUIDE_MAX_BOUNCES): the ray is followed through
+        that many perfect mirrors and smooth glass surfaces, and the record
+        describes the surface the pixel shows (ptRenderDenoiseGuidesSpecular;
+        DESIGN.md §6 row 13).  0: the primary hit (ptRenderDenoiseGuides)."""
+        if int(specular_bounces) == 0:
+            _check(N.hip_lib().ptRenderDenoiseGuides(self.device.handle, scene.handle, self._h, int(camera_index)),
+                   "ptRenderDenoiseGuides")
+            return
+        if int(specular_bounces) < 0:
+            raise ValueError(f"specular_bounces: {specular_bounces}")
+        _check(N.hip_lib().ptRenderDenoiseGuidesSpecular(self.device.handle, scene.handle, self._h, int(camera_index),
+                                                         int(specular_bounces)), "ptRenderDenoiseGuidesSpecular")
 
     def read(self) -> np.ndarray:
         out = np.zeros((self.height, self.width), dtype=N.DENOISE_GUIDE_DTYPE)
@@ -948,7 +958,8 @@ class FrameHistory:
     glue over DenoiseGuides.render and SampleBuffer.reproject."""
 
     def __init__(self, device: "Device", width: int, height: int, params: "ReprojectParameters | None" = None,
-                 follow_shapes: bool = False, validate: "RectifyParameters | bool | None" = None):
+                 follow_shapes: bool = False, validate: "RectifyParameters | bool | None" = None,
+                 specular_bounces: int = 0):
         """follow_shapes: also keep the frame's packed shapes and reproject
         with the motion table between the two frames (shape_motion), so that
         a moved object keeps its history.  The scene's entities must be the
@@ -959,10 +970,15 @@ class FrameHistory:
         any geometry changing loses its weight.  begin_frame() then
         reprojects into a buffer this object owns and leaves the frame's
         sample buffer cleared; merge() joins the two after the frame's first
-        run()."""
+        run().
+        specular_bounces: passed to every guide render this object makes
+        (DenoiseGuides.render).  With follow_shapes a
+        pixel seen through a mirror or smooth glass then carries a tagged shape
+        word, which no motion record covers: it gets no history."""
         self.device = device
         self.width, self.height = int(width), int(height)
         self.params = params
+        self.specular_bounces = int(specular_bounces)
         self.follow_shapes = bool(follow_shapes)
         if validate is None or validate is False:
             self.validate = None
@@ -999,7 +1015,7 @@ class FrameHistory:
                              f"{self.width}x{self.height}")
         camera = ds.cameras[int(camera_index)].copy()
         guides = self._spare
-        guides.render(ds, camera_index)
+        guides.render(ds, camera_index, self.specular_bounces)
         carried = self.buffer is not None
         shapes = ds.shapes.copy() if self.follow_shapes else None
         if carried:

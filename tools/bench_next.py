@@ -43,6 +43,12 @@
   ptRectifyHistory at the same radii (the same frame as its own history,
   held against 2 new rounds), ptRenderSampleBuffer and one a-trous iteration
   of the same run, at 1920x1080 and 3840x2160; every figure three times.
+* specular_guides (ptRenderDenoiseGuidesSpecular, denoise.hip; DESIGN.md §6
+  row 13): kernel ms of the guides through mirrors and smooth glass at 1, 4
+  and 8 bounces beside ptRenderDenoiseGuides of the same run, on C2 at
+  1024x1024, C5 at 2048x1024 (both cameras) and C3 at 1920x1080 (nothing to
+  follow), with the share of followed pixels and the mean chain length;
+  every figure three times.
 * tiles (ptComputeTileStatistics, stats.hip, and ptSetBasicRendererActiveTiles;
   DESIGN.md §6 row 10): kernel ms of the per-tile statistics launch, single
   and pair, beside ptComputeFrameStatistics on the same buffers in the same
@@ -55,7 +61,7 @@
   on all of the job's threads, and the RGB -> spectrum table.
 
 Kernel times are HIP events on the device stream (ptGetKernelStats).
-Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|rectify|despike|preview|openpbr|host ...]
+Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|rectify|despike|specular_guides|preview|openpbr|host ...]
 (default: all).
 """
 import json
@@ -576,6 +582,47 @@ def despike(pt, dev):
     return out
 
 
+def specular_guides(pt, dev):
+    """Per scene and camera: plain_ms (ptRenderDenoiseGuides) and
+    bounces{1,4,8}_ms (ptRenderDenoiseGuidesSpecular) in the same run, each a
+    list: the mean of 10 timed calls after a warm-up call, taken three times
+    in turn.  chain_at_least[k - 1]: the pixels whose records differ between
+    caps k - 1 and k, i.e. whose chain follows at least k surfaces;
+    followed_share = chain_at_least[0] / pixels; mean_chain: the mean number
+    of followed surfaces over those pixels at cap 8."""
+    out = {}
+    for cid, W, H, cameras in ((2, 1024, 1024, (0,)), (5, 2048, 1024, (0, 1)), (3, 1920, 1080, (0,))):
+        scene = pt.Scene.config(cid)
+        ds = pt.DeviceScene(dev)
+        ds.update(scene)
+        for camera in cameras:
+            guides = pt.DenoiseGuides(dev, W, H)
+            longer, prev = [], None
+            for cap in range(9):
+                guides.render(ds, camera, specular_bounces=cap)
+                rec = guides.read().view(np.uint8).reshape(H * W, -1)
+                if prev is not None:
+                    longer.append(int((rec != prev).any(axis=1).sum()))
+                prev = rec
+            res = {"pixels": W * H, "chain_at_least": longer, "followed_share": round(longer[0] / (W * H), 5),
+                   "mean_chain": round(sum(longer) / longer[0], 3) if longer[0] else 0.0}
+            runs = {"plain_ms": lambda: guides.render(ds, camera)}
+            for b in (1, 4, 8):
+                runs[f"bounces{b}_ms"] = lambda b=b: guides.render(ds, camera, specular_bounces=b)
+            for key in runs:
+                res[key] = []
+            for _ in range(3):
+                for key, fn in runs.items():
+                    fn()   # warm
+                    ms, _ = timed(dev, K_GUIDES, fn, 10)
+                    res[key].append(round(ms, 4))
+            out[f"c{cid}_camera{camera}_{W}x{H}"] = res
+            guides.close()
+        ds.close()
+        scene.close()
+    return out
+
+
 def preview(pt, dev):
     out = {}
     modes = {"base_color": pt.PREVIEW_RENDER_MODE_BASE_COLOR, "shaded": pt.PREVIEW_RENDER_MODE_BASE_COLOR_SHADED,
@@ -656,7 +703,7 @@ def host_builds(pt):
 def main():
     pt = load()
     entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "tiles": tiles, "reproject": reproject, "reproject_moving": reproject_moving,
-               "rectify": rectify, "despike": despike,
+               "rectify": rectify, "despike": despike, "specular_guides": specular_guides,
                "preview": preview, "openpbr": openpbr}
     want = sys.argv[1:] or list(entries) + ["host"]
     dev = pt.Device(0)

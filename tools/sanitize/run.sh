@@ -43,6 +43,7 @@ run asan_reproject "$A" reproject
 run asan_reproject_moving "$A" reproject_moving
 run asan_rectify "$A" rectify
 run asan_despike "$A" despike
+run asan_guides "$A" guides
 PT_BVH_THREADS=8 run tsan_bvh "$T" bvh 300000
 run tsan_render "$T" render
 PT_BVH_THREADS=8 run asan_bvh "$A" bvh 200000

@@ -42,11 +42,19 @@
 //                               denormal images from 1x1 to 67x45, every Radius
 //                               and Rank, MinNeighbours from Rank to every
 //                               neighbour, Scale 0, Floor > 0; rejected arguments
+//   san_driver guides           include/pt_guides.h's classification and bounce
+//                               functions: every material type, roughness on
+//                               both sides of the bound and NaN, bounce counts
+//                               up to and past the cap; unit, grazing (c = 0
+//                               included), zero, NaN, infinite and denormal
+//                               vectors; indices 1, below 1, 0, negative, NaN
+//                               and infinite; the restart's packed round trip
 #include "../../path-tracer_amd/csrc/scene/scene.hpp"
 #include "../../path-tracer_amd/csrc/scene/configs.hpp"
 #include "../../path-tracer_amd/csrc/scene/image.hpp"
 #include "../../oracle/pt_oracle.h"
 #include "../../include/pt_scene.h"
+#include "../../include/pt_guides.h"
 
 #include <cmath>
 #include <cstdio>
@@ -760,9 +768,108 @@ static int Despike()
     return bad != 0;
 }
 
+// include/pt_guides.h on the host: the functions the
+// guide kernel's SPECULAR instantiation calls per hit.
+static int Guides()
+{
+    const float nan = std::nanf(""), inf = INFINITY, tiny = 1e-42f;
+    int bad = 0;
+    size_t calls = 0, followed = 0, refracted = 0, mirrored = 0, finite = 0;
+    // classification
+    const uint32_t types[] = {PT_MATERIAL_TYPE_BASIC_DIFFUSE, PT_MATERIAL_TYPE_BASIC_METAL, PT_MATERIAL_TYPE_BASIC_TRANSLUCENT,
+                              PT_MATERIAL_TYPE_OPENPBR, 4u, 0xFFFFFFFFu};
+    const float roughs[] = {0.0f, -0.0f, tiny, 9.99e-4f, 1e-3f, 1.001e-3f, 1.0f, -1.0f, inf, -inf, nan};
+    const uint32_t caps[] = {0u, 1u, 4u, PT_GUIDE_MAX_BOUNCES, PT_GUIDE_MAX_BOUNCES + 1u, 0xFFFFFFFFu};
+    for (uint32_t type : types)
+        for (float r : roughs)
+            for (uint32_t cap : caps)
+                for (uint32_t b = 0; b <= PT_GUIDE_MAX_BOUNCES + 1u; b++) {
+                    const int f = pt_guide_followed(type, r, b, cap);
+                    const int want = b < cap && (type == PT_MATERIAL_TYPE_BASIC_METAL || type == PT_MATERIAL_TYPE_BASIC_TRANSLUCENT) &&
+                                     r < 1e-3f;
+                    bad += f != want;
+                    bad += pt_guide_candidate(type) != (type == 1u || type == 2u);
+                    if (pt_guide_candidate(type))
+                        bad += pt_guide_roughness_word(type) != (type == 1u ? (uint32_t)PT_BASIC_METAL_ROUGHNESS : (uint32_t)PT_BASIC_TRANSLUCENT_ROUGHNESS);
+                    followed += f;
+                    calls++;
+                }
+    // the tag and the shape word over the whole 16-bit range of shape indices
+    for (uint32_t s = 0; s < 65536u; s += 257u) {
+        const uint32_t tag = pt_guide_tag(0u, s);
+        bad += tag != s + 1u || pt_guide_tag(tag, (s + 5u) & 0xFFFFu) != tag;
+        bad += pt_guide_shape_word(tag, 65535u - s) != ((tag << 16) | (65535u - s)) || pt_guide_shape_word(0u, s) != s;
+    }
+    bad += pt_f2u(pt_guide_total(5.0f, -0.0f, 0u)) != 0x80000000u || pt_guide_total(5.0f, 2.0f, 1u) != 7.0f;
+    // directions: frames and rays, well formed and not
+    std::mt19937 rng(13);
+    std::uniform_real_distribution<float> U(-1.0f, 1.0f);
+    // A frame after its packed round trips is orthonormal to within twice the packed form's 6.5e-5, and
+    // the checks below hold to a small multiple of that.
+    const float tol = 1e-3f;
+    struct frame { pt3 N, TX; bool unit; };
+    std::vector<frame> frames = {{v3(0, 0, 1), v3(1, 0, 0), true}, {v3(0, -1, 0), v3(0, 0, -1), true},
+                                 {v3(0, 0, 0), v3(1, 0, 0), false}, {v3(0, 0, 1), v3(0, 0, 0), false},
+                                 {v3(nan, 0, 1), v3(1, 0, 0), false}, {v3(0, 0, 1), v3(nan, nan, nan), false},
+                                 {v3(inf, 0, 0), v3(0, 1, 0), false}, {v3(tiny, tiny, tiny), v3(tiny, 0, 0), false},
+                                 {v3(0, 0, 1e30f), v3(1e30f, 0, 0), false}};
+    for (int i = 0; i < 40; i++) {
+        pt3 N = normalize(v3(U(rng), U(rng), U(rng)));
+        pt3 T = normalize(cross(pt_abs(N.x) < 0.9f ? v3(1, 0, 0) : v3(0, 1, 0), N));
+        frames.push_back({pt_reproject_unpack_unit(pt_reproject_pack_unit(N)), pt_reproject_unpack_unit(pt_reproject_pack_unit(T)), true});
+    }
+    const float etas[] = {1.0f, 1.5f, 2.4f, 1.0003f, 0.999f, 0.5f, 0.0f, -0.0f, -1.5f, tiny, 1e30f, inf, nan};
+    for (const frame& F : frames) {
+        const pt3 TY = cross(F.N, F.TX);
+        std::vector<pt3> rays = {F.N, -F.N, F.TX, -F.TX, TY,                               // along the normal; c = 0 exactly
+                                 F.TX + 1e-8f * F.N, F.TX - 1e-8f * F.N, normalize(F.TX + 1e-4f * F.N),   // grazing
+                                 normalize(F.TX - 1e-4f * F.N), v3(0, 0, 0), v3(nan, 0, 0), v3(inf, 0, 0), v3(tiny, 0, tiny)};
+        for (int i = 0; i < 30; i++) rays.push_back(normalize(v3(U(rng), U(rng), U(rng))));
+        for (size_t r = 0; r < rays.size(); r++) {
+            const pt3 V = rays[r];
+            const bool unit_ray = r < 5 || (r >= 7 && r < 9) || r >= 13;
+            for (uint32_t type : types) {
+                for (float eta : etas) {
+                    const pt3 W = pt_guide_direction(type, eta, F.N, F.TX, V);
+                    pt3 O = v3(1, 2, 3), V2 = V;
+                    pt_guide_restart(&O, &V2, 2.5f, W);
+                    calls++;
+                    const bool ok = W.x == W.x && W.y == W.y && W.z == W.z && pt_reproject_finite(W.x) &&
+                                    pt_reproject_finite(W.y) && pt_reproject_finite(W.z);
+                    finite += ok;
+                    if (!(F.unit && unit_ray)) continue;
+                    const float c = -dot(V, F.N);
+                    const pt3 Mirror = V + (2.0f * c) * F.N;
+                    const bool glass = type == PT_MATERIAL_TYPE_BASIC_TRANSLUCENT;
+                    const float rel = c < 0.0f ? eta : 1.0f / eta;
+                    const bool bends = glass && 1.0f - (rel * rel) * (1.0f - c * c) > 0.0f;
+                    (bends ? refracted : mirrored)++;
+                    if (!bends) {
+                        bad += !(length(W - Mirror) < tol);                          // metal, every other type, TIR, bad index
+                    } else if (eta >= 0.1f && eta <= 10.0f && c != 0.0f) {
+                        // (an index whose square overflows gives infinite components, and c = 0 exactly gives
+                        // cr = 0 and a tangential W of length rel: both defined, both normalised or dropped by
+                        // the packed round trip, neither held to the identities below)
+                        bad += !(pt_abs(length(W) - 1.0f) < tol);                    // |In|^2 = rel^2 (1 - c^2) + k = 1
+                        bad += !(dot(W, F.N) * dot(V, F.N) >= -tol);                  // through the surface
+                        if (eta == 1.0f) bad += !(length(W - V) < tol);              // no interface: straight on
+                        // Snell, on the tangential parts: |W_t| = rel |V_t|
+                        const pt3 Vt = V - dot(V, F.N) * F.N, Wt = W - dot(W, F.N) * F.N;
+                        bad += !(pt_abs(length(Wt) - rel * length(Vt)) < tol * (1.0f + rel));
+                    }
+                    if (ok && length(W) > 0.5f) bad += !(pt_abs(length(V2) - 1.0f) < 1e-5f);   // the round trip gives a unit vector
+                }
+            }
+        }
+    }
+    std::printf("guides: %zu calls, %zu followed, %zu refracted, %zu mirrored, %zu finite directions: %d checks wrong\n",
+                calls, followed, refracted, mirrored, finite, bad);
+    return bad != 0;
+}
+
 int main(int argc, char** argv)
 {
-    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise|stats|tile_stats|reproject|reproject_moving|rectify|despike ...\n"); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: san_driver decode|model|scene|render|bvh|denoise|stats|tile_stats|reproject|reproject_moving|rectify|despike|guides ...\n"); return 2; }
     std::string cmd = argv[1];
     if (cmd == "decode") return Decode(argc - 2, argv + 2);
     if (cmd == "model") return Model(argc - 2, argv + 2);
@@ -776,6 +883,7 @@ int main(int argc, char** argv)
     if (cmd == "reproject_moving") return ReprojectMoving();
     if (cmd == "rectify") return Rectify();
     if (cmd == "despike") return Despike();
+    if (cmd == "guides") return Guides();
     std::fprintf(stderr, "unknown command %s\n", cmd.c_str());
     return 2;
 }
