@@ -658,6 +658,28 @@ int ptCheckFastDivision(pt_device* device, uint64_t n, uint32_t seed, uint64_t* 
  * IEEE quotient 1.0f / d; returns the number of bit mismatches (must be 0). */
 int ptCheckFastReciprocal(pt_device* device, uint64_t* mismatches);
 
+/* Test probe: evaluates operation `op` of pt_numerics.h (PT_NUM_*) on the
+ * device over n elements, calling the functions of pt_fp.h and pt_device.hpp
+ * as the kernels do.  a, b, c are the operand words (a float's bit pattern or
+ * the integer itself); an operand the op does not read may be NULL.  out
+ * receives n * pt_numerics_outputs(op) words, element i first.  The host's
+ * counterpart is the oracle's oracle_fp_eval; tests compare the two bit for
+ * bit.  Blocks.  Fails, launching and writing nothing, on a NULL device, an
+ * unknown op, or n > 0 with out or a needed operand NULL; n == 0 succeeds. */
+int ptEvalNumerics(pt_device* device, uint32_t op, uint32_t n, const uint32_t* a, const uint32_t* b,
+                   const uint32_t* c, uint32_t* out);
+
+/* Test probe: SampleTexture (scene.glsl.inc:181-205) of the uploaded scene's
+ * texture texture_index[i] at uv[2 i], uv[2 i + 1] -> rgba[4 i ..], n samples.
+ * wrap selects the texel wrap: 0 = the signed remainder (every scene), 1 =
+ * the two-select form of the lean shade kernel, which is exact only when
+ * every atlas placement lies in [0, 1] and is refused for a scene whose mask
+ * has PT_SHADE_TEXWRAP.  Blocks.  Fails, launching and writing nothing, on a
+ * NULL argument (with n > 0), a scene of another device or without packs,
+ * wrap > 1, or a texture index >= the scene's texture count. */
+int ptSampleTextures(pt_device* device, pt_scene* scene, uint32_t n, const uint32_t* texture_index,
+                     const float* uv, uint32_t wrap, float* rgba);
+
 /* Diagnostic: runs the extend step on the renderer's current rays with
  * traversal counters.  It writes the same hit records the next Run's extend
  * writes first, so the render is not perturbed.  out = {rays, lane steps, wave steps x 64, internal nodes,

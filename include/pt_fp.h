@@ -12,10 +12,13 @@
  *     gfx950 — hipcc's default div/sqrt lowering — and x86 SSE), compiled with
  *     -ffp-contract=off on both compilers (no FMA, no reassociation);
  *   - exp/log/sin/cos/atan2/asin are the polynomial kernels below, written
- *     with an explicit evaluation order (errors vs. libm are pinned by
- *     tests/test_fp_conventions.py);
- *   - min/max follow IEEE minNum/maxNum (a NaN operand loses), which is what
- *     gfx950's v_min_f32/v_max_f32 and C fminf/fmaxf do;
+ *     with an explicit evaluation order (errors against float64 are pinned
+ *     by tests/test_numerics.py and, over every exponent, cut point and
+ *     denormal, by tests/test_numerics_sweep.py; the device's bits are held
+ *     to the host's by tests/test_gpu_numerics.py);
+ *   - min/max follow IEEE minNum/maxNum (a quiet NaN operand loses) with -0
+ *     ordered below +0, which is what gfx950's v_min_f32/v_max_f32 do and
+ *     what pt_min/pt_max make of C fminf/fmaxf on the host;
  *   - normalize(v) = v * (1/sqrt(dot(v,v))), dot is evaluated left to right;
  *   - mix(x,y,a) = x*(1-a) + y*a (the GLSL / glm formula);
  *   - packSnorm2x16 rounds half away from zero (glm's round()).
@@ -56,8 +59,19 @@ PT_HD float pt_u2f(uint32_t x) { union { float f; uint32_t u; } c; c.u = x; retu
 
 /* --- scalar helpers ---------------------------------------------------------- */
 
+/* minNum / maxNum with the zeros ordered, -0 below +0, as gfx950's v_min_f32 /
+ * v_max_f32 order them.  C leaves fminf(-0, +0) to the library (glibc on x86
+ * answers by operand order), so the host settles equal operands itself: they
+ * are the same number, whose bits either way give, or zeros of both signs,
+ * where OR keeps the sign bit for min and AND drops it for max
+ * (tests/test_gpu_numerics.py holds the two sides together). */
+#ifdef __HIP_DEVICE_COMPILE__
 PT_HD float pt_min(float a, float b) { return fminf(a, b); }
 PT_HD float pt_max(float a, float b) { return fmaxf(a, b); }
+#else
+PT_HD float pt_min(float a, float b) { return a == b ? pt_u2f(pt_f2u(a) | pt_f2u(b)) : fminf(a, b); }
+PT_HD float pt_max(float a, float b) { return a == b ? pt_u2f(pt_f2u(a) & pt_f2u(b)) : fmaxf(a, b); }
+#endif
 PT_HD float pt_abs(float a) { return fabsf(a); }
 PT_HD float pt_sqrt(float a) { return sqrtf(a); }
 PT_HD float pt_floor(float a) { return floorf(a); }

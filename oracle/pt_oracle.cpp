@@ -9,6 +9,7 @@
 #include "pt_oracle.h"
 #include "../include/pt_cie.h"
 #include "../include/pt_glsl.h"
+#include "../include/pt_numerics.h"
 
 #include <atomic>
 #include <cstring>
@@ -1784,6 +1785,40 @@ void oracle_sample_observer(float lambda, float out[3])
 {
     pt3 v = SampleStandardObserver(lambda);
     out[0] = v.x; out[1] = v.y; out[2] = v.z;
+}
+
+int oracle_fp_eval(uint32_t op, uint32_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out)
+{
+    const uint32_t operands = pt_numerics_operands(op), outputs = pt_numerics_outputs(op);
+    if (operands == 0 || op == PT_NUM_FAST_RCP || op == PT_NUM_XDIV) return -1;   // unknown, or device-only
+    if (n && (!out || !a || (operands > 1 && !b) || (operands > 2 && !c))) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t ua = a[i], ub = operands > 1 ? b[i] : 0u, uc = operands > 2 ? c[i] : 0u;
+        uint32_t* r = out + (size_t)i * outputs;
+        if (pt_numerics_eval(op, ua, ub, uc, r)) continue;
+        if (op == PT_NUM_PACK_UNIT_VECTOR) {
+            r[0] = PackUnitVector(v3(pt_u2f(ua), pt_u2f(ub), pt_u2f(uc)));
+        } else {   // PT_NUM_UNPACK_UNIT_VECTOR
+            const pt3 V = UnpackUnitVector(ua);
+            r[0] = pt_f2u(V.x); r[1] = pt_f2u(V.y); r[2] = pt_f2u(V.z);
+        }
+    }
+    return 0;
+}
+
+int oracle_sample_textures(const pt_scene_packs* packs, uint32_t n, const uint32_t* texture_index, const float* uv,
+                           float* rgba)
+{
+    if (!packs || (n && (!texture_index || !uv || !rgba))) return -1;
+    for (uint32_t i = 0; i < n; i++)
+        if (texture_index[i] >= packs->texture_count) return -1;
+    scene_data S(packs);
+    context C(S);
+    for (uint32_t i = 0; i < n; i++) {
+        const pt4 T = C.SampleTexture(texture_index[i], v2(uv[2 * i], uv[2 * i + 1]));
+        rgba[4 * i] = T.x; rgba[4 * i + 1] = T.y; rgba[4 * i + 2] = T.z; rgba[4 * i + 3] = T.w;
+    }
+    return 0;
 }
 
 }  // extern "C"

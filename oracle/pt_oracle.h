@@ -73,6 +73,17 @@ uint32_t oracle_pack_unit_vector(const float v[3]);
 float oracle_unpack_snorm16(uint32_t bits);
 void oracle_unpack_unit_vector(uint32_t packed, float out[3]);
 void oracle_sample_observer(float lambda, float out[3]);
+/* The same kernels in batches: operation `op` of include/pt_numerics.h over n
+ * operand words, with ptEvalNumerics' contract (pt_api.h); the host side of
+ * the device comparison.  Returns 0, or -1 writing nothing on an unknown or
+ * device-only op or a NULL pointer that is needed. */
+int oracle_fp_eval(uint32_t op, uint32_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c, uint32_t* out);
+
+/* SampleTexture (scene.glsl.inc:181-205) of n (texture index, UV) pairs
+ * against the packed scene: ptSampleTextures' counterpart (remainder wrap).
+ * Returns -1, writing nothing, on a NULL pointer or an index out of range. */
+int oracle_sample_textures(const pt_scene_packs* packs, uint32_t n, const uint32_t* texture_index, const float* uv,
+                           float* rgba);
 
 #ifdef __cplusplus
 }

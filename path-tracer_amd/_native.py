@@ -276,6 +276,17 @@ KERNEL_STATS = 9     # the frame and tile statistics passes and the sample-buffe
 STATS_VARIANT_AUTO, STATS_VARIANT_PLAIN, STATS_VARIANT_UNIFORM = 0, 1, 2
 KERNEL_REPROJECT = 10   # ptReprojectSampleBuffer[Moving] and ptRectifyHistory (PT_KERNEL_REPROJECT)
 
+# The numerics probe's operations (include/pt_numerics.h PT_NUM_*: the index is the id).
+NUMERICS_OPS = (
+    "add", "mul", "div", "sqrt", "fma", "min", "max", "clamp", "floor", "fract", "rint", "round_half_away", "mix",
+    "exp", "log", "pow", "sin", "cos", "atan2", "asin", "u32_to_float", "floor_to_int", "random", "random01",
+    "pack_snorm16", "unpack_snorm16", "half_to_float", "pack_unit_vector", "unpack_unit_vector", "fast_rcp", "xdiv",
+)
+NUMERICS_OPERANDS = {"fma": 3, "clamp": 3, "mix": 3, "pack_unit_vector": 3, "add": 2, "mul": 2, "div": 2, "min": 2,
+                     "max": 2, "pow": 2, "atan2": 2, "xdiv": 2}   # every other op reads one operand
+NUMERICS_OUTPUTS = {"random": 2, "unpack_unit_vector": 3}          # every other op writes one word
+NUMERICS_DEVICE_ONLY = ("fast_rcp", "xdiv")                        # pt_device.hpp forms without a host counterpart
+
 _vp = C.c_void_p
 _u32 = C.c_uint32
 _f32 = C.c_float
@@ -437,6 +448,8 @@ HIP_API = {
     "ptSetFrameStatisticsVariant": (_i32, [_vp, _u32]),
     "ptCheckFastDivision": (_i32, [_vp, C.c_uint64, _u32, C.POINTER(C.c_uint64)]),
     "ptCheckFastReciprocal": (_i32, [_vp, C.POINTER(C.c_uint64)]),
+    "ptEvalNumerics": (_i32, [_vp, _u32, _u32, _u32ptr, _u32ptr, _u32ptr, _u32ptr]),
+    "ptSampleTextures": (_i32, [_vp, _vp, _u32, _u32ptr, _fptr, _u32, _fptr]),
     "ptExtendStats": (_i32, [_vp, _vp, C.POINTER(C.c_uint64)]),
     "ptExtendStepCounts": (_i32, [_vp, _vp, _vp]),
     "ptSetProfilingPeriod": (_i32, [_vp, C.c_uint32]),

@@ -22,7 +22,8 @@ SCENE_SRC = sorted((CSRC / "scene").glob("*.cpp"))
 SCENE_HDR = sorted((CSRC / "scene").glob("*.hpp")) + sorted(INCLUDE.glob("*.h"))
 HIP_SRC = [CSRC / "hip" / "kernels.hip", CSRC / "hip" / "resolve.hip", CSRC / "hip" / "preview.hip",
            CSRC / "hip" / "denoise.hip", CSRC / "hip" / "stats.hip", CSRC / "hip" / "reproject.hip",
-           CSRC / "hip" / "rectify.hip", CSRC / "hip" / "despike.hip", CSRC / "hip" / "runtime.hip"]
+           CSRC / "hip" / "rectify.hip", CSRC / "hip" / "despike.hip", CSRC / "hip" / "probe.hip",
+           CSRC / "hip" / "runtime.hip"]
 HIP_HDR = sorted((CSRC / "hip").glob("*.hpp")) + sorted(INCLUDE.glob("*.h"))
 
 SCENE_LIB = PKG / "libptscene.so"

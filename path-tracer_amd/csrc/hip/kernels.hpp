@@ -255,3 +255,9 @@ hipError_t pt_launch_trace_rays(const ptd::dscene& S, uint32_t n, const float* o
 hipError_t pt_launch_finalize(const ptd::dscene& S, uint32_t n, const float4* hit, const float2* hc, float4* rec,
                               float2* uv, hipStream_t st);
 uint32_t pt_extend_stack_cap();
+// Test probes (probe.hip): one numerics operation (include/pt_numerics.h) over
+// n operand words, and SampleTexture at n caller-given UVs with either wrap.
+hipError_t pt_launch_numerics_probe(uint32_t op, uint32_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                                    uint32_t* out, hipStream_t st);
+hipError_t pt_launch_sample_textures(const ptd::dscene& S, uint32_t n, const uint32_t* index, const float2* uv,
+                                     bool unit_wrap, float4* rgba, hipStream_t st);

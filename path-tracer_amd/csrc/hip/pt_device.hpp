@@ -126,9 +126,13 @@ PT_DEV pt3 UnpackUnitVector(uint32_t P)
 
 // Correctly rounded a / b given y = RN(1/b): q = RN(a*y), one FMA residual
 // correction (Markstein) -> RN(a/b).  Outside the guarded range (b or a/b
-// beyond 2^+-100, b = 0, a = 0, NaN) it falls back to IEEE division, so the
-// result is always bit-identical to a / b; ptCheckFastDivision verifies this
-// over >10^9 operand pairs on the device.  (The slab test uses the same
+// beyond 2^+-100, |a| below 2^-100, b = 0, a = 0, NaN) it falls back to IEEE
+// division, so the result is always bit-identical to a / b.  The guard on a
+// keeps the residual r = a - q b exact: r is a multiple of ulp(q) ulp(b),
+// about 2^-46 |a|, which is below the smallest denormal for |a| < 2^-102
+// (tests/test_gpu_numerics.py found such quotients one ulp off).
+// ptCheckFastDivision verifies the equality over >10^9 operand pairs on the
+// device, ptEvalNumerics at chosen ones.  (The slab test uses the same
 // correction without a per-quotient guard: FastQuot below.)
 PT_DEV float RecipForDiv(float b)
 {
@@ -142,7 +146,7 @@ PT_DEV float XDiv(float a, float b, float y)
     float r = __builtin_fmaf(-q, b, a);
     float q1 = __builtin_fmaf(r, y, q);
     float m = pt_abs(q1);
-    if (!(m >= 0x1p-100f && m <= 0x1p100f)) q1 = a / b;
+    if (!(m >= 0x1p-100f && m <= 0x1p100f && pt_abs(a) >= 0x1p-100f)) q1 = a / b;
     return q1;
 }
 

@@ -15,6 +15,7 @@
 #include "../../../include/pt_despike.h"
 #include "../../../include/pt_guides.h"
 #include "../../../include/pt_stats.h"
+#include "../../../include/pt_numerics.h"
 
 #include <rccl/rccl.h>
 
@@ -150,6 +151,7 @@ struct pt_scene {
     dbuf<float> atlas;
     bool atlas_tiled = false;    // atlas in AtlasIndex 4x2-texel blocks
     uint32_t camera_count = 0;
+    uint32_t texture_count = 0;  // texture records on the device (ptSampleTextures checks its indices)
     uint32_t stack_needed = 0;   // max traversal stack entries (TLAS + BLAS)
     uint32_t mats = PT_MATS_ALL | PT_MATS_SCENE; // SceneMaterialMask (shade specialisation)
     uint32_t stack_format = PT_STACK_FORMAT_AUTO;   // ptSetSceneStackFormat (applied at the next update)
@@ -851,6 +853,7 @@ int ptUpdateScene(pt_device* d, pt_scene* s, const pt_scene_packs* p, uint32_t d
     bool first = !s->valid;
     if (first || (dirty & PT_SCENE_DIRTY_TEXTURES)) {
         PT_HIP(s->textures.upload(p->textures, p->texture_count));
+        s->texture_count = p->texture_count;
         size_t atlas_floats = (size_t)p->atlas_width * p->atlas_height * 4 * p->atlas_layer_count;
         s->atlas_tiled = p->atlas && p->atlas_width % 4 == 0 && p->atlas_height % 2 == 0;
         if (s->atlas_tiled) {
@@ -2790,6 +2793,65 @@ int ptCheckFastReciprocal(pt_device* d, uint64_t* mismatches)
     (void)hipFree(dm);
     if (e != hipSuccess) { SetError("ptCheckFastReciprocal: %s", hipGetErrorString(e)); return (int)e; }
     *mismatches = h;
+    return 0;
+}
+
+int ptEvalNumerics(pt_device* d, uint32_t op, uint32_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                   uint32_t* out)
+{
+    if (!d) { SetError("null argument"); return -1; }
+    const uint32_t operands = pt_numerics_operands(op), outputs = pt_numerics_outputs(op);
+    if (operands == 0) { SetError("ptEvalNumerics: unknown op %u", op); return -1; }
+    if (n && (!out || !a || (operands > 1 && !b) || (operands > 2 && !c))) { SetError("null argument"); return -1; }
+    if (n == 0) return 0;
+    PT_HIP(hipSetDevice(d->id));
+    dbuf<uint32_t> d_a, d_b, d_c, d_out;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = d_a.upload(a, n)) != hipSuccess) break;
+        if (operands > 1 && (e = d_b.upload(b, n)) != hipSuccess) break;
+        if (operands > 2 && (e = d_c.upload(c, n)) != hipSuccess) break;
+        if ((e = d_out.alloc((size_t)n * outputs)) != hipSuccess) break;
+        if ((e = pt_launch_numerics_probe(op, n, d_a.ptr, d_b.ptr, d_c.ptr, d_out.ptr, d->stream)) != hipSuccess) break;
+        if ((e = hipStreamSynchronize(d->stream)) != hipSuccess) break;
+        e = hipMemcpy(out, d_out.ptr, (size_t)n * outputs * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    } while (0);
+    if (e != hipSuccess) { SetError("ptEvalNumerics: %s", hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
+int ptSampleTextures(pt_device* d, pt_scene* s, uint32_t n, const uint32_t* texture_index, const float* uv,
+                     uint32_t wrap, float* rgba)
+{
+    if (!d || !s || (n && (!texture_index || !uv || !rgba))) { SetError("null argument"); return -1; }
+    if (s->dev != d) { SetError("ptSampleTextures: scene of another device"); return -1; }
+    if (!s->valid) { SetError("scene has no valid packs"); return -1; }
+    if (wrap > 1) { SetError("ptSampleTextures: wrap %u", wrap); return -1; }
+    if (wrap == 1 && (s->mats & PT_MATS_TEXWRAP)) {
+        SetError("ptSampleTextures: the two-select wrap needs every atlas placement inside [0, 1]");
+        return -1;
+    }
+    for (uint32_t i = 0; i < n; i++)
+        if (texture_index[i] >= s->texture_count) {
+            SetError("ptSampleTextures: texture index %u >= texture count %u", texture_index[i], s->texture_count);
+            return -1;
+        }
+    if (n == 0) return 0;
+    PT_HIP(hipSetDevice(d->id));
+    dbuf<uint32_t> d_index;
+    dbuf<float2> d_uv;
+    dbuf<float4> d_rgba;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = d_index.upload(texture_index, n)) != hipSuccess) break;
+        if ((e = d_uv.upload(reinterpret_cast<const float2*>(uv), n)) != hipSuccess) break;
+        if ((e = d_rgba.alloc(n)) != hipSuccess) break;
+        if ((e = pt_launch_sample_textures(s->d, n, d_index.ptr, d_uv.ptr, wrap == 1, d_rgba.ptr, d->stream)) != hipSuccess)
+            break;
+        if ((e = hipStreamSynchronize(d->stream)) != hipSuccess) break;
+        e = hipMemcpy(rgba, d_rgba.ptr, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost);
+    } while (0);
+    if (e != hipSuccess) { SetError("ptSampleTextures: %s", hipGetErrorString(e)); return (int)e; }
     return 0;
 }
 

@@ -88,6 +88,21 @@ class Device:
         _check(N.hip_lib().ptCheckFastReciprocal(self._h, C.byref(m)), "ptCheckFastReciprocal")
         return int(m.value)
 
+    def eval_numerics(self, op, a, b=None, c=None) -> np.ndarray:
+        """Test probe (ptEvalNumerics): operation `op` (a name of
+        N.NUMERICS_OPS or its id) on the device over uint32 operand words
+        (float bit patterns or integers).  Returns the result words, shape
+        (n,) or (n, outputs) for an op with several."""
+        name = N.NUMERICS_OPS[op] if isinstance(op, int) else op
+        arrays = [None if x is None else np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (a, b, c)]
+        n = len(arrays[0])
+        outputs = N.NUMERICS_OUTPUTS.get(name, 1)
+        out = np.zeros(n * outputs, dtype=np.uint32)
+        ptrs = [None if x is None else N.u32ptr(x) for x in arrays]
+        _check(N.hip_lib().ptEvalNumerics(self._h, N.NUMERICS_OPS.index(name), n, *ptrs, N.u32ptr(out)),
+               "ptEvalNumerics")
+        return out if outputs == 1 else out.reshape(n, outputs)
+
     def close(self):
         if self._h:
             N.hip_lib().ptDestroyDevice(self._h)
@@ -165,6 +180,18 @@ class DeviceScene:
         out = np.zeros(len(v), dtype=N.HIT_RECORD_DTYPE)
         _check(N.hip_lib().ptTraceRays(self.device.handle, self._h, len(v), N.fptr(o), N.u32ptr(v), N.fptr(d),
                                        out.ctypes.data), "ptTraceRays")
+        return out
+
+    def sample_textures(self, texture_index: np.ndarray, uv: np.ndarray, wrap: int = 0) -> np.ndarray:
+        """Test probe (ptSampleTextures): SampleTexture of the uploaded scene
+        at (n, 2) UVs; wrap 0 = remainder, 1 = the lean kernel's two-select
+        form (refused when a placement leaves [0, 1]).  Returns (n, 4)."""
+        t = np.ascontiguousarray(texture_index, dtype=np.uint32).reshape(-1)
+        u = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        assert len(u) == len(t)
+        out = np.zeros((len(t), 4), dtype=np.float32)
+        _check(N.hip_lib().ptSampleTextures(self.device.handle, self._h, len(t), N.u32ptr(t), N.fptr(u), int(wrap),
+                                            N.fptr(out)), "ptSampleTextures")
         return out
 
     def trace_rays_stats(self, origins: np.ndarray, packed_velocities: np.ndarray, durations: np.ndarray):

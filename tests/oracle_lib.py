@@ -59,6 +59,11 @@ def lib():
         L.oracle_unpack_snorm16.restype = f32
         L.oracle_unpack_snorm16.argtypes = [u32]
         L.oracle_sample_observer.argtypes = [f32, fptr]
+        u32p = C.POINTER(C.c_uint32)
+        L.oracle_fp_eval.restype = C.c_int
+        L.oracle_fp_eval.argtypes = [u32, u32, u32p, u32p, u32p, u32p]
+        L.oracle_sample_textures.restype = C.c_int
+        L.oracle_sample_textures.argtypes = [vp, u32, u32p, fptr, fptr]
         L.oracle_resolve.argtypes = [fptr, u32, vp, fptr, C.POINTER(C.c_uint8)]
         L.oracle_preview.argtypes = [vp, vp, fptr, vp, C.POINTER(C.c_uint32)]
         _lib = L
@@ -191,6 +196,35 @@ def pack_unit_vectors(v: np.ndarray) -> np.ndarray:
     out = np.zeros(len(v), dtype=np.uint32)
     for i in range(len(v)):
         out[i] = lib().oracle_pack_unit_vector(v[i].ctypes.data_as(C.POINTER(C.c_float)))
+    return out
+
+
+def fp_eval(op, a, b=None, c=None) -> np.ndarray:
+    """oracle_fp_eval: numerics operation `op` (a name of _native.NUMERICS_OPS)
+    on the host over uint32 operand words; the result words, shape (n,) or
+    (n, outputs).  Device.eval_numerics' counterpart."""
+    from path_tracer_amd import _native as N
+    arrays = [None if x is None else np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (a, b, c)]
+    n = len(arrays[0])
+    outputs = N.NUMERICS_OUTPUTS.get(op, 1)
+    out = np.zeros(n * outputs, dtype=np.uint32)
+    ptrs = [None if x is None else x.ctypes.data_as(C.POINTER(C.c_uint32)) for x in arrays]
+    rc = lib().oracle_fp_eval(N.NUMERICS_OPS.index(op), n, *ptrs, out.ctypes.data_as(C.POINTER(C.c_uint32)))
+    if rc != 0:
+        raise ValueError(f"oracle_fp_eval({op}) refused its arguments")
+    return out if outputs == 1 else out.reshape(n, outputs)
+
+
+def sample_textures(packs, texture_index, uv) -> np.ndarray:
+    """oracle_sample_textures: SampleTexture at (n, 2) UVs -> (n, 4)."""
+    t = np.ascontiguousarray(texture_index, dtype=np.uint32).reshape(-1)
+    u = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+    assert len(u) == len(t)
+    out = np.zeros((len(t), 4), dtype=np.float32)
+    rc = lib().oracle_sample_textures(C.addressof(packs), len(t), t.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                      u.ctypes.data_as(C.POINTER(C.c_float)), out.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise ValueError("oracle_sample_textures refused its arguments")
     return out
 
 

@@ -89,3 +89,52 @@ def test_null_arguments_rejected(pt):
     assert L.ptGetBasicRendererClassLists(None, None) != 0
     out = np.zeros(1, dtype=pt._native.HIT_RECORD_DTYPE)
     assert L.ptTraceRays(None, None, 1, None, None, None, out.ctypes.data) != 0
+    words = np.zeros(4, dtype=np.uint32)
+    wp = words.ctypes.data_as(C.POINTER(C.c_uint32))
+    assert L.ptEvalNumerics(None, 0, 4, wp, wp, None, wp) != 0
+    assert L.ptEvalNumerics(None, 0, 0, None, None, None, None) != 0
+    assert b"null" in L.ptGetLastError()
+    uv = np.zeros(8, dtype=np.float32)
+    fp = uv.ctypes.data_as(C.POINTER(C.c_float))
+    assert L.ptSampleTextures(None, None, 2, wp, fp, 0, fp) != 0
+    assert b"null" in L.ptGetLastError()
+    assert not words.any() and not uv.any()
+
+
+def test_numerics_op_list_matches_header(pt):
+    """_native.NUMERICS_OPS is the PT_NUM_* enum of pt_numerics.h: same names,
+    same ids, and the operand / output counts of its two tables."""
+    N = pt._native
+    text = (INCLUDE / "pt_numerics.h").read_text()
+    enum = dict((m.group(1).lower(), int(m.group(2))) for m in re.finditer(r"\bPT_NUM_(\w+)\s*=\s*(\d+)", text))
+    assert enum.pop("op_count") == len(N.NUMERICS_OPS)
+    assert enum == {name: i for i, name in enumerate(N.NUMERICS_OPS)}
+    assert set(N.NUMERICS_OPERANDS) | set(N.NUMERICS_OUTPUTS) | set(N.NUMERICS_DEVICE_ONLY) <= set(N.NUMERICS_OPS)
+
+
+def test_oracle_batch_evaluation_contract(pt):
+    """oracle_fp_eval / oracle_sample_textures: exported, every host op
+    answers with the table's output count, device-only and unknown ops and
+    missing operands are refused without a write."""
+    import oracle_lib
+    N = pt._native
+    L = oracle_lib.lib()
+    one = np.array([0x3F800000, 0x40000000, 0x3F000000], dtype=np.uint32)
+    for name in N.NUMERICS_OPS:
+        k = N.NUMERICS_OPERANDS.get(name, 1)
+        if name in N.NUMERICS_DEVICE_ONLY:
+            with pytest.raises(ValueError):
+                oracle_lib.fp_eval(name, *([one] * k))
+            continue
+        got = oracle_lib.fp_eval(name, *([one] * k))
+        assert got.shape == ((3,) if N.NUMERICS_OUTPUTS.get(name, 1) == 1 else (3, N.NUMERICS_OUTPUTS[name]))
+        if k > 1:
+            with pytest.raises(ValueError):
+                oracle_lib.fp_eval(name, *([one] * (k - 1) + [None]))
+    assert oracle_lib.fp_eval("add", one, one).tolist() == [0x40000000, 0x40800000, 0x3F800000]
+    out = np.full(3, 0xABCDEF01, dtype=np.uint32)
+    p = one.ctypes.data_as(C.POINTER(C.c_uint32))
+    assert L.oracle_fp_eval(len(N.NUMERICS_OPS), 3, p, p, p, out.ctypes.data_as(C.POINTER(C.c_uint32))) != 0
+    assert L.oracle_fp_eval(0, 3, p, p, p, None) != 0
+    assert np.all(out == 0xABCDEF01)
+    assert L.oracle_sample_textures(None, 0, None, None, None) != 0
