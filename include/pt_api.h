@@ -292,6 +292,32 @@ int                ptSetBasicRendererRoundBatch(pt_basic_renderer* renderer, uin
  * them now.  Default 0. */
 int                ptSetBasicRendererClassLists(pt_basic_renderer* renderer, uint32_t mode);
 int                ptGetBasicRendererClassLists(const pt_basic_renderer* renderer, uint32_t* used);
+/* Ray order (no reference counterpart: where a tile's 256 new rays sit in the
+ * tile's ray records; results are identical in every order).  OCTANT: by
+ * direction octant.  LENGTH: new camera rays first, then continuing rays by
+ * the traversal length predicted for their ray key (include/pt_raykey.h) from
+ * a table the device scene learns on a fixed schedule of training rounds --
+ * the first 16 LENGTH rounds after the table was cleared and every 64th after
+ * them -- so that short rays share waves (DESIGN.md §4 "Length classes").  The
+ * table belongs to the scene: every ptUpdateScene that touches shapes or
+ * meshes clears it, Resets and frames keep it, renderers of one scene share
+ * it.  LENGTH runs where the mesh-only extend loop and the diffuse tile shade
+ * do (a scene that is one mesh instance, no spilled stack, unfused rounds);
+ * elsewhere the renderer keeps OCTANT.  AUTO (default) = LENGTH where it runs.
+ * ptGetBasicRendererRayOrder: the order set and the order the next unfused
+ * rounds use (either pointer may be NULL).
+ * ptReadSceneLengthTable (diagnostic; any pointer may be NULL): the class
+ * 0..6 of each of the PT_RAYKEY_COUNT keys, whether a finalize has written
+ * them since the last clear, and the LENGTH rounds counted since then.
+ * ptReadBasicRendererRayPositions (diagnostic): per slot, the position of its
+ * current ray (high byte) and of its last traced hit (low byte) within its
+ * tile; ptBasicRendererSlotCount entries.  Both reads synchronise. */
+enum { PT_RAY_ORDER_AUTO = 0, PT_RAY_ORDER_OCTANT = 1, PT_RAY_ORDER_LENGTH = 2 };
+int                ptSetBasicRendererRayOrder(pt_basic_renderer* renderer, uint32_t order);
+int                ptGetBasicRendererRayOrder(const pt_basic_renderer* renderer, uint32_t* order, uint32_t* used);
+int                ptReadSceneLengthTable(pt_device* device, pt_scene* scene, uint8_t* classes, uint32_t* trained,
+                                          uint64_t* rounds);
+int                ptReadBasicRendererRayPositions(pt_device* device, pt_basic_renderer* renderer, uint16_t* positions);
 int                ptSetBasicRendererSplit(pt_basic_renderer* renderer, uint32_t groups);
 int                ptGetBasicRendererSplit(const pt_basic_renderer* renderer, uint32_t* groups, uint32_t* timed_tiles,
                                            uint32_t* tiles);
@@ -403,6 +429,9 @@ typedef struct pt_shade_info {
                                    (the separate extend / shade launches; fused rounds do not queue) */
     uint32_t grey_records;      /* 1: live paths keep one Probability float and no stack
                                    (as of the last Reset / Run / state write) */
+    uint32_t ray_order;         /* PT_RAY_ORDER_OCTANT or PT_RAY_ORDER_LENGTH: the order the next
+                                   unfused rounds place new rays in (AUTO resolved, fall-backs applied) */
+    uint32_t length_trained;    /* 1: the scene's length table holds trained classes */
 } pt_shade_info;
 int                ptGetBasicRendererShadeInfo(pt_basic_renderer* renderer, pt_shade_info* info);
 

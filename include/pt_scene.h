@@ -302,6 +302,11 @@ int    ptsStatsPercentileBin(const uint32_t* histogram, double q);
 double ptsStatsLogAverage(const uint32_t* histogram, double q_lo, double q_hi);
 double ptsStatsAutoBrightness(const pt_frame_statistics* stats, double key, double q_lo, double q_hi);
 double ptsStatsNoise(const pt_frame_statistics* stats, double q);
+/* pt_raykey.h's key (0 .. 32 767) of the ray (origin, velocity) over the 8^3
+ * grid of the world bounds [lo, hi]: what the device's length table is
+ * indexed by (pt_api.h ptSetBasicRendererRayOrder).  0xFFFFFFFF on a NULL
+ * argument. */
+uint32_t ptsRayKey(const float origin[3], const float velocity[3], const float lo[3], const float hi[3]);
 
 #ifdef __cplusplus
 }

@@ -42,7 +42,11 @@ class pt_scene_packs(C.Structure):
 class pt_shade_info(C.Structure):
     """pt_shade_info (include/pt_api.h): the shade variant a renderer runs."""
     _fields_ = [("scene_mask", C.c_uint32), ("kernel_mask", C.c_uint32), ("completion_queue", C.c_uint32),
-                ("grey_records", C.c_uint32)]
+                ("grey_records", C.c_uint32), ("ray_order", C.c_uint32), ("length_trained", C.c_uint32)]
+
+
+RAY_ORDER_AUTO, RAY_ORDER_OCTANT, RAY_ORDER_LENGTH = 0, 1, 2   # PT_RAY_ORDER_*
+RAYKEY_COUNT = 32768                                            # PT_RAYKEY_COUNT (include/pt_raykey.h)
 
 
 SHADE_DIFFUSE, SHADE_METAL, SHADE_TRANSLUCENT, SHADE_SCATTER = 1, 2, 4, 8
@@ -367,6 +371,7 @@ SCENE_API = {
     "ptsStatsLogAverage": (C.c_double, [_u32ptr, C.c_double, C.c_double]),
     "ptsStatsAutoBrightness": (C.c_double, [C.POINTER(pt_frame_statistics), C.c_double, C.c_double, C.c_double]),
     "ptsStatsNoise": (C.c_double, [C.POINTER(pt_frame_statistics), C.c_double]),
+    "ptsRayKey": (_u32, [_fptr, _fptr, _fptr, _fptr]),
 }
 
 HIP_API = {
@@ -412,6 +417,10 @@ HIP_API = {
     "ptSetBasicRendererClassLists": (_i32, [_vp, _u32]),
     "ptGetBasicRendererClassLists": (_i32, [_vp, _u32ptr]),
     "ptGetBasicRendererSplit": (_i32, [_vp, _u32ptr, _u32ptr, _u32ptr]),
+    "ptSetBasicRendererRayOrder": (_i32, [_vp, _u32]),
+    "ptGetBasicRendererRayOrder": (_i32, [_vp, _u32ptr, _u32ptr]),
+    "ptReadSceneLengthTable": (_i32, [_vp, _vp, _vp, _u32ptr, C.POINTER(C.c_uint64)]),
+    "ptReadBasicRendererRayPositions": (_i32, [_vp, _vp, _vp]),
     "ptSetBasicRendererOpenPBR": (_i32, [_vp, _i32]),
     "ptGetStats": (_i32, [_vp, _vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "ptTraceRaysStats": (_i32, [_vp, _vp, _u32, _fptr, _u32ptr, _fptr, C.POINTER(C.c_uint64), _vp]),

@@ -20,7 +20,11 @@
 // pos(s); extend runs one thread per position, so a wave traces rays of one
 // octant from one 16x16 pixel tile (0.91x extend time on C3 vs pixel order,
 // tools/exp_reorder.py).  Every ray is still traced and shaded with its own
-// slot's data, so results do not depend on the order.
+// slot's data, so results do not depend on the order.  In LENGTH order
+// (dslots::len_order; one-mesh diffuse scenes) the same sort runs on other
+// keys: new camera rays first, then continuing rays by the traversal length a
+// per-scene table predicts for them, so that a tile's short rays share waves
+// (TileOrderLengthKey; C3 extend 0.84x vs the octant order).
 #include "pt_device.hpp"
 #include "traverse.hpp"
 #include "kernels.hpp"
@@ -818,7 +822,25 @@ PT_DEV uint32_t TileOrderKey(bool valid, pt3 V)
     return valid ? ((V.x < 0.0f ? 1u : 0u) | (V.y < 0.0f ? 2u : 0u) | (V.z < 0.0f ? 4u : 0u)) : 8u;
 }
 
+// LENGTH order (dslots::len_order; DESIGN.md §4 "Length classes"): the same
+// ranking with other keys, so that a tile's short rays share waves and those
+// waves end early.  0 for a new camera ray (every raygen ray, shade's
+// completed paths), 1 + the length class of the ray's key in the scene's
+// table (include/pt_raykey.h) for a continuing ray, 8 outside the image.
+// Camera rays therefore sit at the tile's first positions; their count goes
+// to len_cam, and a training extend skips them (their few shared keys would
+// serialise its atomics).  Until the table is trained a continuing ray's class
+// is its octant, the last two sharing one, which keeps the camera rays first.
+PT_DEV uint32_t TileOrderLengthKey(const dslots& L, bool valid, bool camera, pt3 O, pt3 V)
+{
+    if (!valid) return 8u;
+    if (camera) return 0u;
+    if (!L.len_cls) return 1u + min(TileOrderKey(true, V), PT_RAYKEY_CLASSES - 1u);
+    return 1u + L.len_cls[pt_ray_key(O.x, O.y, O.z, V.x, V.y, V.z, &L.len_bounds)];
+}
+
 // The same for a ray already packed ({O.xyz, PackUnitVector(V)}) with its key.
+template <bool LEN = false>
 PT_DEV void TileOrderStoreKeyed(const dslots& L, uint32_t s, uint32_t key, float4 ray, uint32_t hitbyte)
 {
     __shared__ uint32_t cnt[64];
@@ -845,12 +867,20 @@ PT_DEV void TileOrderStoreKeyed(const dslots& L, uint32_t s, uint32_t key, float
     L.ray[q] = ray;
     L.pos[s] = (uint16_t)((p << 8) | hitbyte);
     L.slotof[q] = (uint8_t)(s & 255u);
+    if constexpr (LEN) {
+        // Key 0's four counts end at lane 3 of the scan: the tile's camera rays.
+        if (threadIdx.x == 3) L.len_cam[s >> 8] = (uint16_t)incl;
+    }
 }
 
-PT_DEV void TileOrderStoreRay(const dslots& L, uint32_t s, bool valid, pt3 O, pt3 V, uint32_t hitbyte)
+// camera: the ray starts a new path (read in LENGTH order only).
+template <bool LEN = false>
+PT_DEV void TileOrderStoreRay(const dslots& L, uint32_t s, bool valid, bool camera, pt3 O, pt3 V, uint32_t hitbyte)
 {
-    TileOrderStoreKeyed(L, s, TileOrderKey(valid, V), make_float4(O.x, O.y, O.z, __uint_as_float(PackUnitVector(V))),
-                        hitbyte);
+    uint32_t key;
+    if constexpr (LEN) key = TileOrderLengthKey(L, valid, camera, O, V);
+    else key = TileOrderKey(valid, V);
+    TileOrderStoreKeyed<LEN>(L, s, key, make_float4(O.x, O.y, O.z, __uint_as_float(PackUnitVector(V))), hitbyte);
 }
 
 // GenerateNewPath (basic_scatter.glsl:7-42) + GenerateCameraRay (scene.glsl.inc:613-655)
@@ -1031,7 +1061,9 @@ __global__ __launch_bounds__(256) void raygen_kernel(dscene S, dslots L, dframe 
         GenerateNewPath(S, L, F, Pm, G, s, x, y, O, V);
         StreamAccum(F, stream)[(size_t)y * F.width + x] = make_float4(0, 0, 0, 0);
     }
-    TileOrderStoreRay(L, s, valid, O, V, L.pos[s] & 255u);
+    // Every ray is a camera ray (LENGTH order: key 0, the tile's whole count).
+    if (L.len_order) TileOrderStoreRay<true>(L, s, valid, true, O, V, L.pos[s] & 255u);
+    else TileOrderStoreRay(L, s, valid, true, O, V, L.pos[s] & 255u);
 }
 
 // State write (ptWriteBasicRendererState): the restored rays of one tile,
@@ -1045,10 +1077,13 @@ __global__ __launch_bounds__(256) void restore_rays_kernel(dslots L, dframe F, c
     uint32_t x, y;
     const bool valid = SlotPixel(F, s, x, y);
     const float4 r = rays[s - tile0 * 256];
-    const uint32_t key = TileOrderKey(valid, UnpackUnitVector(__float_as_uint(r.w)));
+    const pt3 V = UnpackUnitVector(__float_as_uint(r.w));
     L.hit[s] = make_float4(0.0f, __uint_as_float(SHAPE_INDEX_NONE), 0.0f, 0.0f);
     L.uv[s] = make_float2(0.0f, 0.0f);
-    TileOrderStoreKeyed(L, s, key, r, 0u);
+    // LENGTH order: a restored ray counts as a continuing one (the state does
+    // not say which rays start a path).
+    if (L.len_order) TileOrderStoreKeyed<true>(L, s, TileOrderLengthKey(L, valid, false, v3(r.x, r.y, r.z), V), r, 0u);
+    else TileOrderStoreKeyed(L, s, TileOrderKey(valid, V), r, 0u);
 }
 
 // Ray sources of the extend kernel: the renderer's slots, or the arrays of
@@ -1133,15 +1168,39 @@ constexpr bool kRendererSource = std::is_same<Src, ray_source_slots>::value;
 // for the lanes whose ray takes the exact fast division and one for the
 // others (usually none); each lane's ray is traced as before, only beside
 // other lanes.
-template <bool SPILL, int CAP, class E, bool MESH = false, class Src>
+//
+// TRAIN (the renderer's mesh-only loop in LENGTH order, on the table's
+// training rounds): the lane counts its steps and adds them, capped at 255,
+// and 1 to its ray key's sum and count (integer atomics without a return:
+// the sums do not depend on the order).  Positions below the tile's camera
+// count are skipped (TileOrderLengthKey).
+template <bool SPILL, int CAP, class E, bool MESH = false, bool TRAIN = false, class Src>
 PT_DEV void ExtendRay(const dscene& S, const Src& src, tstack<SPILL, CAP, E>& st, uint32_t slot)
 {
+    static_assert(!TRAIN || (MESH && kRendererSource<Src>), "training counts the mesh-only loop's steps");
     pt3 O, V;
     float D;
     uint32_t cls = 0;
     if (src.load(slot, O, V, D)) {
         lane_state Ln;
-        if constexpr (MESH) {
+        if constexpr (MESH && TRAIN) {
+            uint32_t steps = 0;
+            MeshBegin(S, Ln, O, V, D);
+            if (Ln.exact) {
+                while (!MeshStep<true>(S, Ln, st)) steps++;
+            } else {
+                while (!MeshStep<false>(S, Ln, st)) steps++;
+            }
+            if (Ln.Shape == 0xFFFFFFFEu) Ln.Shape = 0;
+            if ((slot & 255u) >= src.L.len_cam[slot >> 8]) {
+                // The ray again from its record: nothing of it stays live over the loop.
+                const float4 r = src.L.ray[slot];
+                const pt3 W = UnpackUnitVector(__float_as_uint(r.w));
+                const uint32_t key = pt_ray_key(r.x, r.y, r.z, W.x, W.y, W.z, &src.L.len_bounds);
+                atomicAdd(&src.L.len_sum[key], min(steps, 255u));
+                atomicAdd(&src.L.len_cnt[key], 1u);
+            }
+        } else if constexpr (MESH) {
             MeshBegin(S, Ln, O, V, D);
             if (Ln.exact) {
                 while (!MeshStep<true>(S, Ln, st)) {}
@@ -1170,7 +1229,7 @@ PT_DEV void ExtendRay(const dscene& S, const Src& src, tstack<SPILL, CAP, E>& st
 }
 
 // One tile of extend: thread i traces the ray at position tile*256 + i.
-template <class Src, bool SPILL, int CAP, class E, bool MESH = false>
+template <class Src, bool SPILL, int CAP, class E, bool MESH = false, bool TRAIN = false>
 PT_DEV void ExtendTile(const dscene& S, const Src& src, uint32_t n, uint32_t* spill, uint32_t spill_stride, E* smem,
                        uint32_t tile, bool timed, const float4* nc = nullptr, uint32_t ncn = 0)
 {
@@ -1183,7 +1242,7 @@ PT_DEV void ExtendTile(const dscene& S, const Src& src, uint32_t n, uint32_t* sp
     st.stride = spill_stride;
     st.nc = nc;
     st.ncn = ncn;
-    ExtendRay<SPILL, CAP, E, MESH>(S, src, st, slot);
+    ExtendRay<SPILL, CAP, E, MESH, TRAIN>(S, src, st, slot);
     if constexpr (kRendererSource<Src>) {
         if (timed && (threadIdx.x & 63u) == 0)
             src.L.tilecost[tile * 4 + (threadIdx.x >> 6)] = (uint32_t)(__builtin_amdgcn_s_memtime() - t0);
@@ -1206,7 +1265,8 @@ PT_DEV uint32_t NodeCacheFill(const dscene& S, float4* nc)
 // hold the loop without a spill; C3 extend on the two 32-bit stack formats
 // 0.3142-0.3149 -> 0.3036-0.3038 and 0.3313-0.3328 -> 0.3228-0.3243 ms.  The
 // one with the cache takes 56 either way.)
-template <class Src, bool SPILL, int MINW, int CAP, class E = uint32_t, bool NC = false, bool MESH = false>
+template <class Src, bool SPILL, int MINW, int CAP, class E = uint32_t, bool NC = false, bool MESH = false,
+          bool TRAIN = false>
 __global__ __launch_bounds__(256, (MESH && !NC) ? 8 : MINW) void extend_kernel(dscene S, Src src, uint32_t n,
                                                                                uint32_t* spill, uint32_t spill_stride)
 {
@@ -1227,7 +1287,7 @@ __global__ __launch_bounds__(256, (MESH && !NC) ? 8 : MINW) void extend_kernel(d
             timed = true;
         }
     }
-    ExtendTile<Src, SPILL, CAP, E, MESH>(S, src, n, spill, spill_stride, smem, tile, timed, ncache, ncn);
+    ExtendTile<Src, SPILL, CAP, E, MESH, TRAIN>(S, src, n, spill, spill_stride, smem, tile, timed, ncache, ncn);
 }
 
 // Longest-first dispatch order for the next extend: tiles by their slowest
@@ -1279,6 +1339,73 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* cost, 
     for (uint32_t i = threadIdx.x; i < nt; i += 1024) {
         const uint32_t t = pt_tile_group_tile(tiles, groups, group, i);
         order[start + atomicAdd(&count[key(t)], 1u)] = t;
+    }
+}
+
+// The length table's finalize (LENGTH order), one block after a call's
+// training rounds.  A key's mean steps in 1/16 (steps are capped at 255: 4 096
+// values); the classes are cut at the count-weighted 1/7 .. 6/7 quantiles of
+// the means -- bound j = the first mean whose keys, with those below, hold
+// j/7 of the rays -- and a key's class is the number of bounds below its mean.
+// Keys without a sample take the middle class.  A count above 2^16 is shifted
+// down with its sum until it fits, so the words never overflow and old rounds
+// fade; everything is integer arithmetic on order-independent sums, so the
+// classes are the same on every run.
+constexpr uint32_t LEN_MEAN_BINS = 4096;
+__global__ __launch_bounds__(1024) void length_classes_kernel(uint32_t* sum, uint32_t* cnt, uint8_t* cls)
+{
+    __shared__ unsigned long long hist[LEN_MEAN_BINS];
+    __shared__ unsigned long long part[1024];
+    __shared__ uint32_t bound[PT_RAYKEY_CLASSES - 1];
+    const uint32_t t = threadIdx.x;
+    for (uint32_t i = t; i < LEN_MEAN_BINS; i += 1024) hist[i] = 0;
+    if (t < PT_RAYKEY_CLASSES - 1) bound[t] = LEN_MEAN_BINS;
+    __syncthreads();
+    auto mean = [](uint32_t s, uint32_t c) { return min((s << 4) / c, LEN_MEAN_BINS - 1u); };   // c < 2^16, s <= 255 c
+    for (uint32_t i = t; i < PT_RAYKEY_COUNT; i += 1024) {
+        uint32_t c = cnt[i], s = sum[i];
+        if (c > 65535u) {
+            const uint32_t sh = 16u - (uint32_t)__clz(c);
+            c >>= sh;
+            s >>= sh;
+            cnt[i] = c;
+        }
+        s = min(s, 255u * c);   // a sum that wrapped in a very long call
+        sum[i] = s;
+        if (c) atomicAdd(&hist[mean(s, c)], (unsigned long long)c);
+    }
+    __syncthreads();
+    // Thread t owns bins 4 t .. 4 t + 3; a block scan of the threads' sums.
+    unsigned long long h[4], own = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) { h[k] = hist[4 * t + k]; own += h[k]; }
+    part[t] = own;
+    __syncthreads();
+    for (uint32_t o = 1; o < 1024; o <<= 1) {
+        const unsigned long long v = t >= o ? part[t - o] : 0ull;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    const unsigned long long total = part[1023];
+    unsigned long long before = part[t] - own;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) {
+        const unsigned long long after = before + h[k];
+        for (uint32_t j = 1; j < PT_RAYKEY_CLASSES; j++)
+            if (before * PT_RAYKEY_CLASSES < j * total && after * PT_RAYKEY_CLASSES >= j * total) bound[j - 1] = 4 * t + k;
+        before = after;
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < PT_RAYKEY_COUNT; i += 1024) {
+        const uint32_t c = cnt[i];   // this thread's own writes above
+        uint32_t k = PT_RAYKEY_CLASSES / 2;
+        if (c) {
+            const uint32_t m = mean(sum[i], c);
+            k = 0;
+            for (uint32_t j = 0; j < PT_RAYKEY_CLASSES - 1; j++) k += m > bound[j] ? 1u : 0u;
+        }
+        cls[i] = (uint8_t)k;
     }
 }
 
@@ -1666,7 +1793,8 @@ PT_DEV void CompletionQueue(const dscene& S, const dslots& L, const dframe& F, c
 // One tile of shade (basic_scatter.glsl:main for the tile's 256 slots).
 // COMPACT: completion queue, for scenes whose paths also end at surfaces
 // (ShadeCompact, runtime.hip).
-template <uint32_t MATS, bool COMPACT = false>
+// LEN: the tile's new rays in LENGTH order (TileOrderLengthKey).
+template <uint32_t MATS, bool COMPACT = false, bool LEN = false>
 PT_DEV void ShadeTile(const dscene& S, const dslots& L, const dframe& F, const dparams& Pm, uint32_t tile)
 {
     // One block per tile, no early exit (TileOrder).  ShadeOrder: thread u
@@ -1695,10 +1823,10 @@ PT_DEV void ShadeTile(const dscene& S, const dslots& L, const dframe& F, const d
     uint64_t cm = __ballot(completed);
     if ((threadIdx.x & 63u) == 0) L.done[(base | threadIdx.x) >> 6] += (uint32_t)__popcll(cm);
     if constexpr (COMPACT) CompletionQueue(S, L, F, Pm, s, completed, cm, cstate, csample, cactnone, O, V);
-    TileOrderStoreRay(L, s, valid, O, V, p16 >> 8);
+    TileOrderStoreRay<LEN>(L, s, valid, completed, O, V, p16 >> 8);
 }
 
-template <uint32_t MATS, bool COMPACT>
+template <uint32_t MATS, bool COMPACT, bool LEN = false>
 __global__ __launch_bounds__(256, ShadeMinWaves<MATS>()) void shade_kernel(dscene S, dslots L, dframe F,
                                                                                     dparams Pm)
 {
@@ -1706,7 +1834,7 @@ __global__ __launch_bounds__(256, ShadeMinWaves<MATS>()) void shade_kernel(dscen
     // also shade more hits (C5 shade -3 %).
     if (L.stop && *L.stop) return;   // a guarded round past the frame's target
     ShadeStatsBegin();
-    ShadeTile<MATS, COMPACT>(S, L, F, Pm, L.order ? L.order[blockIdx.x] : blockIdx.x);
+    ShadeTile<MATS, COMPACT, LEN>(S, L, F, Pm, L.order ? L.order[blockIdx.x] : blockIdx.x);
     ShadeStatsEnd();
 }
 
@@ -2140,10 +2268,50 @@ hipError_t pt_launch_zero_unowned(float4* accum, uint32_t width, uint32_t height
     return hipGetLastError();
 }
 
-hipError_t pt_launch_extend(const ptd::dscene& S, const ptd::dslots& L, const ptd::dframe& F, uint32_t* spill,
-                            hipStream_t st)
+// The training instantiations (ExtendRay's TRAIN): the mesh-only loop's
+// unspilled variants, as LaunchExtendE picks them.
+template <class E>
+static void LaunchExtendTrain(const ptd::dscene& S, const ptd::ray_source_slots& src, uint32_t n, uint32_t blocks,
+                              hipStream_t st)
 {
+    using Src = ptd::ray_source_slots;
+    if constexpr (sizeof(E) == 2) {
+        if (S.node_cache) {
+            hipLaunchKernelGGL((ptd::extend_kernel<Src, false, PT_EXTEND_MINW, PT_EXTEND_CAP, E, true, true, true>),
+                               dim3(blocks), dim3(256), 0, st, S, src, n, nullptr, n);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((ptd::extend_kernel<Src, false, PT_EXTEND_MINW, PT_EXTEND_CAP, E, false, true, true>),
+                       dim3(blocks), dim3(256), 0, st, S, src, n, nullptr, n);
+}
+
+bool pt_length_train_supported(const ptd::dscene& S, bool spill) { return S.single_mesh != 0 && !spill; }
+
+bool pt_length_order_supported(uint32_t scene_mats)
+{
+    const uint32_t m = pt_shade_mats(scene_mats);
+    return m == PT_MATS_DIFFUSE || m == (PT_MATS_DIFFUSE | PT_MATS_SCENE);
+}
+
+hipError_t pt_launch_extend(const ptd::dscene& S, const ptd::dslots& L, const ptd::dframe& F, uint32_t* spill,
+                            hipStream_t st, bool train)
+{
+    if (train) {
+        if (!pt_length_train_supported(S, spill != nullptr) || !L.len_sum || !L.len_cnt || !L.len_cam)
+            return hipErrorNotSupported;
+        if (L.n == 0 || L.tile_count == 0) return hipSuccess;
+        if (S.stack16) LaunchExtendTrain<uint16_t>(S, ptd::ray_source_slots{L, F}, L.n, L.tile_count, st);
+        else LaunchExtendTrain<uint32_t>(S, ptd::ray_source_slots{L, F}, L.n, L.tile_count, st);
+        return hipGetLastError();
+    }
     return LaunchExtend(S, ptd::ray_source_slots{L, F}, L.n, L.tile_count, spill, st);
+}
+
+hipError_t pt_launch_length_classes(uint32_t* sum, uint32_t* cnt, uint8_t* cls, hipStream_t st)
+{
+    hipLaunchKernelGGL(ptd::length_classes_kernel, dim3(1), dim3(1024), 0, st, sum, cnt, cls);
+    return hipGetLastError();
 }
 
 // Fused rounds (round_kernel): the default extend variant's LDS stack
@@ -2256,6 +2424,17 @@ static void LaunchShade(const ptd::dscene& S, const ptd::dslots& L, const ptd::d
                         uint32_t scene_mats, hipStream_t st)
 {
     const uint32_t blocks = L.tile_count;
+    // LENGTH order (pt_length_order_supported's masks): the instantiation
+    // that keys a tile's new rays by camera / length class.
+    if (L.len_order) {
+        if (pt_shade_mats(scene_mats) == PT_MATS_DIFFUSE)
+            hipLaunchKernelGGL((ptd::shade_kernel<PT_MATS_DIFFUSE, COMPACT, true>), dim3(blocks), dim3(256), 0, st, S, L,
+                               F, P);
+        else
+            hipLaunchKernelGGL((ptd::shade_kernel<PT_MATS_DIFFUSE | PT_MATS_SCENE, COMPACT, true>), dim3(blocks),
+                               dim3(256), 0, st, S, L, F, P);
+        return;
+    }
     switch (pt_shade_mats(scene_mats)) {
     case PT_MATS_DIFFUSE:
         hipLaunchKernelGGL((ptd::shade_kernel<PT_MATS_DIFFUSE, COMPACT>), dim3(blocks), dim3(256), 0, st, S, L, F, P);
@@ -2283,6 +2462,7 @@ hipError_t pt_launch_shade(const ptd::dscene& S, const ptd::dslots& L, const ptd
                            uint32_t scene_mats, bool compact, hipStream_t st)
 {
     if (L.n == 0 || L.tile_count == 0) return hipSuccess;
+    if (L.len_order && (!pt_length_order_supported(scene_mats) || !L.len_cam)) return hipErrorNotSupported;
     if (compact) LaunchShade<true>(S, L, F, P, scene_mats, st);
     else LaunchShade<false>(S, L, F, P, scene_mats, st);
     return hipGetLastError();

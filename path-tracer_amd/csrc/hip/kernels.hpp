@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "../../../include/pt_packed.h"
 #include "../../../include/pt_api.h"
+#include "../../../include/pt_raykey.h"
 
 namespace ptd {
 
@@ -36,6 +37,14 @@ struct dslots {
     const uint32_t* stop = nullptr;   // guarded rounds (ptRenderFrame's last rounds): set -> the launch returns
     uint32_t n;
     uint32_t tile_count;    // n / 256: one block per tile
+    // Ray order LENGTH (TileOrder, kernels.hip; include/pt_raykey.h).  All
+    // null / zero in OCTANT order.
+    uint32_t len_order = 0;             // 1: a tile's new camera rays first, then continuing rays by length class
+    const uint8_t* len_cls = nullptr;   // the scene's class per ray key (0..6); null until the table is trained
+    uint16_t* len_cam = nullptr;        // per tile: its camera rays, which sit at the tile's first positions
+    uint32_t* len_sum = nullptr;        // a training extend adds every continuing ray's steps to its key's sum
+    uint32_t* len_cnt = nullptr;        // ... and 1 to its count
+    pt_raykey_bounds len_bounds{};      // the key's grid over the scene's world bounds
 };
 
 struct dframe {
@@ -69,8 +78,21 @@ struct dparams {
 
 hipError_t pt_launch_raygen(const ptd::dscene& S, const ptd::dslots& L, const ptd::dframe& F, const ptd::dparams& P,
                             hipStream_t st);
+// train: the training instantiation (LENGTH order; L.len_sum, len_cnt and
+// len_cam set), which pt_length_train_supported has for the scene.
 hipError_t pt_launch_extend(const ptd::dscene& S, const ptd::dslots& L, const ptd::dframe& F, uint32_t* spill,
-                            hipStream_t st);
+                            hipStream_t st, bool train = false);
+// Ray order LENGTH: the scenes whose extend has a training instantiation (the
+// mesh-only loop without a spilled stack) and the shade masks whose tile shade
+// has a LENGTH instantiation (pt_launch_shade takes it when L.len_order is
+// set); the renderer keeps OCTANT order elsewhere.
+bool pt_length_train_supported(const ptd::dscene& S, bool spill);
+bool pt_length_order_supported(uint32_t scene_mats);
+// The table's finalize (one block): per-key mean steps in fixed point, the
+// classes from the count-weighted 1/7 .. 6/7 quantiles of the means, the
+// middle class for keys without a sample; counts above 2^16 are halved with
+// their sums until they fit.
+hipError_t pt_launch_length_classes(uint32_t* sum, uint32_t* cnt, uint8_t* cls, hipStream_t st);
 hipError_t pt_launch_extend_stats(const ptd::dscene& S, const ptd::dslots& L, const ptd::dframe& F, uint32_t* spill,
                                   unsigned long long* out, uint32_t* steps, hipStream_t st);
 // Material-type mask of a scene (shade kernel specialisation).

@@ -161,6 +161,16 @@ struct pt_scene {
     uint32_t blas16_bits = 0;
     uint32_t extend_form = PT_EXTEND_FORM_AUTO;     // ptSetSceneExtendForm (applied at the next update)
     bool one_mesh = false;       // the uploaded scene is one mesh instance (OneMeshScene; d.mesh_root, d.mesh_from)
+    // Traversal-length table (ray order LENGTH; LengthTable below): per ray key
+    // the steps and rays the training rounds added and the class made of them.
+    // Cleared by every update that touches shapes or meshes; kept across
+    // Resets, frames and renderers (a function of the geometry).
+    dbuf<uint32_t> len_sum, len_cnt;
+    dbuf<uint8_t> len_cls;
+    pt_raykey_bounds len_bounds{};
+    bool len_trained = false;    // a finalize has written len_cls since the last clear
+    bool len_pending = false;    // training rounds ran since the last finalize
+    uint64_t len_rounds = 0;     // LENGTH rounds issued since the last clear (the training schedule's clock)
     bool valid = false;
 };
 
@@ -248,6 +258,9 @@ struct pt_basic_renderer {
     dbuf<float4> accx;                  // streams > 1: each stream's accumulator (streams x width x height)
     uint64_t rays = 0;                  // rays traced since the last Reset
     dbuf<uint32_t> spill;
+    uint32_t ray_order = PT_RAY_ORDER_AUTO;   // ptSetBasicRendererRayOrder
+    dbuf<uint16_t> len_cam;             // LENGTH order: camera rays per tile (kernels.hip TileOrderLengthKey)
+    bool len_cam_stale = true;          // len_cam does not describe the rays in place: zero it before a training round
 };
 
 struct pt_comm {
@@ -918,6 +931,24 @@ int ptUpdateScene(pt_device* d, pt_scene* s, const pt_scene_packs* p, uint32_t d
                                        s->vertex_attr.ptr, s->vertex_v.ptr, d->stream));
     }
     if (first || (dirty & PT_SCENE_DIRTY_CAMERAS)) PT_HIP(s->cameras.upload(p->cameras, p->camera_count));
+    // The traversal-length table describes the geometry: a change of shapes or
+    // meshes clears it and re-lays the key grid over the new world bounds (the
+    // TLAS root's box; an axis without a finite extent gets one cell).
+    if (first || (dirty & (PT_SCENE_DIRTY_SHAPES | PT_SCENE_DIRTY_MESHES))) {
+        float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+        if (p->shape_node_count && p->shape_nodes)
+            for (int k = 0; k < 3; k++) { lo[k] = p->shape_nodes[0].Minimum[k]; hi[k] = p->shape_nodes[0].Maximum[k]; }
+        s->len_bounds = pt_raykey_make_bounds(lo, hi);
+        PT_HIP(s->len_sum.alloc(PT_RAYKEY_COUNT));
+        PT_HIP(s->len_cnt.alloc(PT_RAYKEY_COUNT));
+        PT_HIP(s->len_cls.alloc(PT_RAYKEY_COUNT));
+        PT_HIP(hipMemsetAsync(s->len_sum.ptr, 0, PT_RAYKEY_COUNT * sizeof(uint32_t), d->stream));
+        PT_HIP(hipMemsetAsync(s->len_cnt.ptr, 0, PT_RAYKEY_COUNT * sizeof(uint32_t), d->stream));
+        PT_HIP(hipMemsetAsync(s->len_cls.ptr, PT_RAYKEY_CLASSES / 2, PT_RAYKEY_COUNT, d->stream));
+        s->len_trained = false;
+        s->len_pending = false;
+        s->len_rounds = 0;
+    }
 
     ptd::dscene& D = s->d;
     D.g = *p->globals;
@@ -1251,6 +1282,8 @@ static int SyncRecordForm(pt_device* d, pt_basic_renderer* r)
     return 0;
 }
 
+static int SyncRayOrder(pt_basic_renderer* r);   // the ray order section below
+
 // ResetBasicRenderer (basic.cpp:285-304)
 int ptResetBasicRenderer(pt_device* d, pt_basic_renderer* r)
 {
@@ -1261,6 +1294,10 @@ int ptResetBasicRenderer(pt_device* d, pt_basic_renderer* r)
     r->grey = GreyForm(r);
     r->grey_blocked = false;
     r->slots.prob1 = r->grey ? r->prob1.ptr : nullptr;
+    // Raygen places every tile's rays in the renderer's order and, in LENGTH
+    // order, writes every tile's camera count.
+    if (int e = SyncRayOrder(r)) return e;
+    r->len_cam_stale = false;
     PT_TIMED(d, PT_KERNEL_RAYGEN,
              pt_launch_raygen(r->scene->d, r->slots, Frame(r), Params(r, r->params.FrameIndex), d->stream));
     PT_HIP(hipMemsetAsync(r->done.ptr, 0, (size_t)(r->slots.n / 64 + 1) * 4, d->stream));
@@ -1396,6 +1433,88 @@ static bool ClassLists(const pt_basic_renderer* r)
 // single-stream rounds alike).
 static bool ClassListRounds(const pt_basic_renderer* r) { return SplitGroups(r) > 1 && ClassLists(r); }
 
+// --- ray order (ptSetBasicRendererRayOrder; DESIGN.md §4 "Length classes") ------
+// LENGTH places a tile's new rays by the traversal length their key's class
+// predicts (kernels.hip TileOrderLengthKey), from the scene's table.  It runs
+// where extend has a training instantiation (the mesh-only loop, no spilled
+// stack) and the tile shade a LENGTH one; elsewhere the renderer keeps OCTANT
+// and reports it.  The fused round kernels and the class-list shade place
+// rays as before: class lists never meet LENGTH (their masks differ), and a
+// fused round leaves the camera counts stale (len_cam_stale).
+//
+// Training schedule, counted in the LENGTH rounds issued on the scene since
+// its table was cleared: the first LEN_TRAIN_FIRST rounds and every
+// LEN_TRAIN_PERIOD-th after them run the training extend; guarded rounds and
+// fused rounds never train.  A finalize follows the training rounds of a call
+// on the device stream, once every tile group has joined, so the classes
+// change only between calls and every run of the same calls sees the same
+// classes in the same rounds.  A batch of tile-group rounds that holds the
+// first training rounds is cut after them, so that its other rounds already
+// use the classes.
+constexpr uint64_t LEN_TRAIN_FIRST = 16, LEN_TRAIN_PERIOD = 64;
+
+static bool LengthSupported(const pt_basic_renderer* r)
+{
+    return pt_length_train_supported(r->scene->d, Spills(r)) && pt_length_order_supported(ShadeMats(r));
+}
+
+// AUTO: LENGTH wherever it is supported -- the unfused tile shade of diffuse
+// one-mesh scenes (C3, C4), where it measured faster.
+static bool LengthOrder(const pt_basic_renderer* r)
+{
+    return r->ray_order != PT_RAY_ORDER_OCTANT && LengthSupported(r);
+}
+
+// The order of the launches that follow, in the renderer's slots (every
+// round's view is cut from them).
+static int SyncRayOrder(pt_basic_renderer* r)
+{
+    ptd::dslots& L = r->slots;
+    if (!LengthOrder(r)) {
+        if (L.len_order) r->len_cam_stale = true;
+        L.len_order = 0;
+        L.len_cls = nullptr;
+        L.len_cam = nullptr;
+        L.len_sum = L.len_cnt = nullptr;
+        return 0;
+    }
+    pt_scene* s = r->scene;
+    if (!r->len_cam.ptr) {
+        PT_HIP(r->len_cam.alloc((size_t)L.tile_count + 1));
+        r->len_cam_stale = true;
+    }
+    if (!L.len_order) r->len_cam_stale = true;
+    L.len_order = 1;
+    L.len_cls = s->len_trained ? s->len_cls.ptr : nullptr;
+    L.len_cam = r->len_cam.ptr;
+    L.len_sum = s->len_sum.ptr;
+    L.len_cnt = s->len_cnt.ptr;
+    L.len_bounds = s->len_bounds;
+    return 0;
+}
+
+// Whether the next LENGTH round trains (and counts it).
+static bool LengthTrainRound(pt_basic_renderer* r)
+{
+    if (!r->slots.len_order) return false;
+    pt_scene* s = r->scene;
+    const uint64_t t = s->len_rounds++;
+    const bool train = t < LEN_TRAIN_FIRST || t % LEN_TRAIN_PERIOD == 0;
+    if (train) s->len_pending = true;
+    return train;
+}
+
+// After a call's rounds, on the device stream (the tile groups joined).
+static int LengthFinalize(pt_device* d, pt_basic_renderer* r)
+{
+    pt_scene* s = r->scene;
+    if (!r->slots.len_order || !s->len_pending) return 0;
+    PT_HIP(pt_launch_length_classes(s->len_sum.ptr, s->len_cnt.ptr, s->len_cls.ptr, d->stream));
+    s->len_pending = false;
+    s->len_trained = true;
+    return SyncRayOrder(r);
+}
+
 // Rewrites the dispatch order for K groups, each group's tiles in its own
 // segment in natural order; with an active tile set, a segment's active tiles
 // first (group_active of them), the inactive ones behind.  Waits for the
@@ -1522,6 +1641,14 @@ static int BeginRounds(pt_device* d, pt_basic_renderer* r, uint32_t K, uint64_t 
     // their tiles against the positions, and the class lists' gathers by slot
     // lose their coherence (C2 -4 % measured, profiles/r05_exp2).
     S.lists = !S.fused && ClassLists(r) && (K > 1 || SplitGroups(r) > 1);
+    // Ray order of the call's launches.  Camera counts that do not describe
+    // the rays in place (a change of order, fused rounds in between) are
+    // zeroed before a round may train: it then trains every ray once.
+    if (int e = SyncRayOrder(r)) return e;
+    if (r->slots.len_order && r->len_cam_stale && !S.fused) {
+        PT_HIP(hipMemsetAsync(r->len_cam.ptr, 0, ((size_t)r->slots.tile_count + 1) * sizeof(uint16_t), d->stream));
+        r->len_cam_stale = false;
+    }
     return 0;
 }
 
@@ -1561,16 +1688,18 @@ static int Resort(pt_basic_renderer* r, uint32_t g0, uint32_t g1, hipStream_t st
 // then the tile-local or the class-list shade.  timed: kernel timing takes
 // the launches (those on the device stream of a sampled round).
 static int IssueRound(pt_device* d, pt_basic_renderer* r, const round_setup& S, const ptd::dslots& L,
-                      const ptd::dparams& P, hipStream_t st, bool timed, uint32_t K = 1, uint32_t g = 0)
+                      const ptd::dparams& P, hipStream_t st, bool timed, uint32_t K = 1, uint32_t g = 0,
+                      bool train = false)
 {
     event_pair ep{};
     if (S.fused) {
         if (int e = BeginTimed(d, PT_KERNEL_ROUND, ep, timed)) return e;
         PT_HIP(pt_launch_round(r->scene->d, L, S.F, P, S.mats, st));
+        r->len_cam_stale = true;   // the fused shade places rays by octant
         return EndTimed(d, ep);
     }
     if (int e = BeginTimed(d, PT_KERNEL_EXTEND, ep, timed)) return e;
-    PT_HIP(pt_launch_extend(r->scene->d, L, S.F, L.spill, st));
+    PT_HIP(pt_launch_extend(r->scene->d, L, S.F, L.spill, st, train));
     if (int e = EndTimed(d, ep)) return e;
     if (int e = BeginTimed(d, PT_KERNEL_SHADE, ep, timed)) return e;
     if (S.lists) {
@@ -1600,6 +1729,7 @@ static int IssueBatch(pt_device* d, pt_basic_renderer* r, const round_setup& S, 
     event_pair ep{};
     if (int e = BeginTimed(d, PT_KERNEL_ROUNDS, ep, sampled, n)) return e;
     PT_HIP(pt_launch_rounds(r->scene->d, L, S.F, P, S.mats, d->stream));
+    r->len_cam_stale = true;   // the fused shade places rays by octant
     if (int e = EndTimed(d, ep)) return e;
     if (!Masked(r))
         if (int e = Resort(r, 0, r->order_groups, d->stream)) return e;
@@ -1633,12 +1763,13 @@ int ptRunBasicRenderer(pt_device* d, pt_basic_renderer* r, uint32_t rounds)
     const ptd::dparams P = Params(r, seed);
     for (uint32_t i = 0; i < rounds; i++) {
         const round_tick tick = NextRound(d, r);
-        if (int e = IssueRound(d, r, S, L, P, d->stream, tick.sampled)) return e;
+        const bool train = !S.fused && LengthTrainRound(r);
+        if (int e = IssueRound(d, r, S, L, P, d->stream, tick.sampled, 1, 0, train)) return e;
         if (tick.sort)
             if (int e = Resort(r, 0, r->order_groups, d->stream)) return e;
         RoundsDone(d, r, 1, 0, RoundSlots(r));
     }
-    return 0;
+    return LengthFinalize(d, r);
 }
 
 // Tile groups on concurrent streams: k consecutive rounds (FrameIndex + 1 ...
@@ -1665,9 +1796,10 @@ static int SplitRounds(pt_device* d, pt_basic_renderer* r, const round_setup& S,
         for (uint64_t i = 0; i < k; i++) {
             const ptd::dparams P = Params(r, r->params.FrameIndex + 1);
             const round_tick tick = NextRound(d, r);
+            const bool train = LengthTrainRound(r);   // every group of the round, or none
             for (uint32_t g = 0; g < K; g++) {
                 if (G[g].tile_count == 0) continue;   // a group without an active tile
-                if (int e = IssueRound(d, r, S, G[g], P, St[g], g == 0 && tick.sampled, K, g)) return e;
+                if (int e = IssueRound(d, r, S, G[g], P, St[g], g == 0 && tick.sampled, K, g, train)) return e;
                 if (tick.sort)
                     if (int e = Resort(r, g, g + 1, St[g])) return e;
             }
@@ -1713,7 +1845,19 @@ static int RunRounds(pt_device* d, pt_basic_renderer* r, uint64_t k)
         }
         return 0;
     }
-    if (K > 1) return SplitRounds(d, r, S, k, K);
+    if (K > 1) {
+        // LENGTH order: the table's first training rounds end in a finalize
+        // of their own, so that the batch's other rounds run on its classes.
+        while (k > 0) {
+            uint64_t n = k;
+            if (r->slots.len_order && r->scene->len_rounds < LEN_TRAIN_FIRST)
+                n = std::min<uint64_t>(k, LEN_TRAIN_FIRST - r->scene->len_rounds);
+            if (int e = SplitRounds(d, r, S, n, K)) return e;
+            if (int e = LengthFinalize(d, r)) return e;
+            k -= n;
+        }
+        return 0;
+    }
     for (uint64_t i = 0; i < k; i++)
         if (int e = ptRunBasicRenderer(d, r, 1)) return e;
     return 0;
@@ -1744,6 +1888,49 @@ int ptGetBasicRendererClassLists(const pt_basic_renderer* r, uint32_t* used)
 {
     if (!r || !used) { SetError("ptGetBasicRendererClassLists: null argument"); return -1; }
     *used = ClassListRounds(r) ? 1u : 0u;
+    return 0;
+}
+
+int ptSetBasicRendererRayOrder(pt_basic_renderer* r, uint32_t order)
+{
+    if (!r || order > PT_RAY_ORDER_LENGTH) {
+        SetError("ptSetBasicRendererRayOrder: bad argument (0 automatic, 1 octant, 2 length)");
+        return -1;
+    }
+    r->ray_order = order;
+    return 0;
+}
+
+int ptGetBasicRendererRayOrder(const pt_basic_renderer* r, uint32_t* order, uint32_t* used)
+{
+    if (!r) { SetError("ptGetBasicRendererRayOrder: null renderer"); return -1; }
+    if (used && (!r->scene || !r->scene->valid)) {
+        SetError("renderer: scene has no valid packs (call ptUpdateScene)");
+        return -1;
+    }
+    if (order) *order = r->ray_order;
+    if (used) *used = LengthOrder(r) ? PT_RAY_ORDER_LENGTH : PT_RAY_ORDER_OCTANT;
+    return 0;
+}
+
+int ptReadSceneLengthTable(pt_device* d, pt_scene* s, uint8_t* classes, uint32_t* trained, uint64_t* rounds)
+{
+    if (!d || !s) { SetError("ptReadSceneLengthTable: null argument"); return -1; }
+    if (!s->valid) { SetError("scene has no valid packs (call ptUpdateScene)"); return -1; }
+    PT_HIP(hipSetDevice(d->id));
+    PT_WAIT(d);
+    if (classes) PT_HIP(hipMemcpy(classes, s->len_cls.ptr, PT_RAYKEY_COUNT, hipMemcpyDeviceToHost));
+    if (trained) *trained = s->len_trained ? 1u : 0u;
+    if (rounds) *rounds = s->len_rounds;
+    return 0;
+}
+
+int ptReadBasicRendererRayPositions(pt_device* d, pt_basic_renderer* r, uint16_t* positions)
+{
+    if (!d || !r || !positions) { SetError("ptReadBasicRendererRayPositions: null argument"); return -1; }
+    PT_HIP(hipSetDevice(d->id));
+    PT_WAIT(d);
+    if (r->slots.n) PT_HIP(hipMemcpy(positions, r->pos.ptr, (size_t)r->slots.n * 2, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -2105,6 +2292,11 @@ int ptWriteBasicRendererStreamState(pt_device* d, pt_basic_renderer* r, uint32_t
     PT_HIP(hipMemcpy(r->act.ptr + s0, act.data(), n * 8, hipMemcpyHostToDevice));
     dbuf<float4> stage;
     PT_HIP(stage.upload(ray.data(), n));
+    if (int e = SyncRayOrder(r)) return e;
+    if (r->slots.len_order && r->len_cam_stale) {   // the other streams' tiles (BeginRounds)
+        PT_HIP(hipMemsetAsync(r->len_cam.ptr, 0, ((size_t)r->slots.tile_count + 1) * sizeof(uint16_t), d->stream));
+        r->len_cam_stale = false;
+    }
     PT_HIP(pt_launch_restore_rays(r->slots, Frame(r), stage.ptr, s0 / 256, T, d->stream));
     PT_WAIT(d);   // the launch reads stage
     return 0;
@@ -2157,6 +2349,8 @@ int ptGetBasicRendererShadeInfo(pt_basic_renderer* r, pt_shade_info* info)
     info->kernel_mask = pt_shade_mats(ShadeMats(r));
     info->completion_queue = ShadeCompact(r) ? 1u : 0u;
     info->grey_records = r->grey ? 1u : 0u;
+    info->ray_order = LengthOrder(r) ? PT_RAY_ORDER_LENGTH : PT_RAY_ORDER_OCTANT;
+    info->length_trained = r->scene->len_trained ? 1u : 0u;
     return 0;
 }
 

@@ -4,6 +4,7 @@
 #include "configs.hpp"
 #include "image.hpp"
 #include "../../../include/pt_scene.h"
+#include "../../../include/pt_raykey.h"
 
 #include <cstring>
 #include <exception>
@@ -414,5 +415,13 @@ int ptsLoadSpectrumTable(const char* path)
 }
 
 void ptsSetSpectrumTablePath(const char* path) { SetSpectrumTablePath(path ? path : ""); }
+
+// pt_raykey.h's key of one ray over the grid of the bounds [lo, hi].
+uint32_t ptsRayKey(const float origin[3], const float velocity[3], const float lo[3], const float hi[3])
+{
+    if (!origin || !velocity || !lo || !hi) return 0xFFFFFFFFu;
+    const pt_raykey_bounds B = pt_raykey_make_bounds(lo, hi);
+    return pt_ray_key(origin[0], origin[1], origin[2], velocity[0], velocity[1], velocity[2], &B);
+}
 
 }  // extern "C"

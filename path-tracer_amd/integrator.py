@@ -158,6 +158,16 @@ class DeviceScene:
             buf = (C.c_char * (packs.shape_count * N.SHAPE_DTYPE.itemsize)).from_address(packs.shapes)
             self.shapes = np.frombuffer(buf, dtype=N.SHAPE_DTYPE).copy()
 
+    def length_table(self) -> dict:
+        """{classes, trained, rounds}: the scene's traversal-length table, one
+        class 0..6 per ray key, whether it was trained since the last clear and
+        the LENGTH rounds counted since then (diagnostic, ptReadSceneLengthTable)."""
+        cls = np.zeros(N.RAYKEY_COUNT, dtype=np.uint8)
+        t, n = C.c_uint32(0), C.c_uint64(0)
+        _check(N.hip_lib().ptReadSceneLengthTable(self.device.handle, self._h, cls.ctypes.data, C.byref(t), C.byref(n)),
+               "ptReadSceneLengthTable")
+        return {"classes": cls, "trained": bool(t.value), "rounds": int(n.value)}
+
     @property
     def stack_needed(self) -> int:
         """Traversal stack entries the uploaded scene can need (TLAS + BLAS depth)."""
@@ -1172,6 +1182,27 @@ class BasicRenderer:
         _check(N.hip_lib().ptGetBasicRendererClassLists(self._h, C.byref(u)), "ptGetBasicRendererClassLists")
         return bool(u.value)
 
+    def set_ray_order(self, order: int):
+        """Where a tile's new rays sit (ptSetBasicRendererRayOrder): 0
+        automatic, 1 by direction octant, 2 by predicted traversal length.
+        Results are identical in every order."""
+        _check(N.hip_lib().ptSetBasicRendererRayOrder(self._h, int(order)), "ptSetBasicRendererRayOrder")
+
+    def ray_order(self) -> dict:
+        """{order, used}: the order set and the one the next unfused rounds
+        use, 1 octant or 2 length (ptGetBasicRendererRayOrder)."""
+        o, u = C.c_uint32(0), C.c_uint32(0)
+        _check(N.hip_lib().ptGetBasicRendererRayOrder(self._h, C.byref(o), C.byref(u)), "ptGetBasicRendererRayOrder")
+        return {"order": int(o.value), "used": int(u.value)}
+
+    def ray_positions(self) -> np.ndarray:
+        """Per slot, the position of its ray (high byte) and of its last hit
+        (low byte) within its tile (diagnostic, ptReadBasicRendererRayPositions)."""
+        out = np.zeros(self._slot_count(), dtype=np.uint16)
+        _check(N.hip_lib().ptReadBasicRendererRayPositions(self.device.handle, self._h, out.ctypes.data),
+               "ptReadBasicRendererRayPositions")
+        return out
+
     def set_active_tiles(self, mask: "np.ndarray | None"):
         """The tiles the following rounds run on (ptSetBasicRendererActiveTiles):
         a (tiles_y, tiles_x) array, non-zero = active (tile_mask_of_region
@@ -1298,7 +1329,8 @@ class BasicRenderer:
         info = N.pt_shade_info()
         _check(N.hip_lib().ptGetBasicRendererShadeInfo(self._h, C.byref(info)), "ptGetBasicRendererShadeInfo")
         return {"scene_mask": int(info.scene_mask), "kernel_mask": int(info.kernel_mask),
-                "completion_queue": bool(info.completion_queue), "grey_records": bool(info.grey_records)}
+                "completion_queue": bool(info.completion_queue), "grey_records": bool(info.grey_records),
+                "ray_order": int(info.ray_order), "length_trained": bool(info.length_trained)}
 
     def close(self):
         if self._h:

@@ -24,6 +24,8 @@ def main():
     ap.add_argument("--fused", type=int, default=0, help="ptSetBasicRendererFusedRounds mode (0 never, 1 auto)")
     ap.add_argument("--batch", type=int, default=1, help="round batch for the timed rounds (1: one launch pair each)")
     ap.add_argument("--split", type=int, default=0, help="tile groups (ptSetBasicRendererSplit; 0 automatic, 1 off)")
+    ap.add_argument("--ray-order", type=int, default=0,
+                    help="ptSetBasicRendererRayOrder (0 automatic, 1 octant, 2 length); needs a build that has it")
     a = ap.parse_args()
     if a.lib:
         os.environ["PT_HIP_LIB"] = str((ROOT / a.lib) if not os.path.isabs(a.lib) else a.lib)
@@ -40,6 +42,8 @@ def main():
     r.set_fused_rounds(a.fused)
     r.set_round_batch(a.batch)
     r.set_split(a.split)
+    if a.ray_order:
+        r.set_ray_order(a.ray_order)
     r.RenderFlags = info.render_flags
     r.PathTerminationProbability = info.termination_probability
     r.reset()
