@@ -1,6 +1,6 @@
 /*
  * pt_raykey.h — the key of a ray in the traversal-length table (TileOrder's
- * LENGTH mode, kernels.hip; DESIGN.md §4 "Length classes").
+ * LENGTH mode, path.hpp; DESIGN.md §4 "Length classes").
  *
  * A ray's key is the cell of its origin in an 8 x 8 x 8 grid over the scene's
  * world bounds (origins outside are clamped to the border cells) times the

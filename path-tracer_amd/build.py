@@ -20,10 +20,10 @@ INCLUDE = ROOT / "include"
 
 SCENE_SRC = sorted((CSRC / "scene").glob("*.cpp"))
 SCENE_HDR = sorted((CSRC / "scene").glob("*.hpp")) + sorted(INCLUDE.glob("*.h"))
-HIP_SRC = [CSRC / "hip" / "kernels.hip", CSRC / "hip" / "resolve.hip", CSRC / "hip" / "preview.hip",
-           CSRC / "hip" / "denoise.hip", CSRC / "hip" / "stats.hip", CSRC / "hip" / "reproject.hip",
-           CSRC / "hip" / "rectify.hip", CSRC / "hip" / "despike.hip", CSRC / "hip" / "probe.hip",
-           CSRC / "hip" / "runtime.hip"]
+# The slowest to compile first: one object per source, compiled concurrently.
+HIP_SRC = [CSRC / "hip" / f"{name}.hip" for name in (
+    "shade", "rounds", "extend", "kernels", "resolve", "preview", "denoise", "stats", "reproject", "rectify",
+    "despike", "probe", "runtime")]
 HIP_HDR = sorted((CSRC / "hip").glob("*.hpp")) + sorted(INCLUDE.glob("*.h"))
 
 SCENE_LIB = PKG / "libptscene.so"
@@ -56,15 +56,20 @@ def build_scene(force=False, verbose=True):
     return SCENE_LIB
 
 
+def hip_flags(extra=()):
+    """The compile flags of every HIP source (tools/kernel_diff.py compiles with the same)."""
+    return [f"--offload-arch={ARCH}", "-std=c++17", "-O3", "-fPIC",
+            # -fno-slp-vectorize: no v_pk_* f32 packing (and its operand moves);
+            # shade 0.164 -> 0.156 ms on C3, extend unchanged (tools/gpu_ab.sh).
+            "-ffp-contract=off", "-fno-gpu-rdc", "-munsafe-fp-atomics", "-fno-slp-vectorize",
+            "-Wno-unused-result", *extra]
+
+
 def build_hip(force=False, verbose=True, out=None, extra=()):
     out = Path(out) if out else HIP_LIB
     if not force and not _stale(out, HIP_SRC + HIP_HDR + [Path(__file__)]):
         return out
-    flags = [f"--offload-arch={ARCH}", "-std=c++17", "-O3", "-fPIC",
-             # -fno-slp-vectorize: no v_pk_* f32 packing (and its operand moves);
-             # shade 0.164 -> 0.156 ms on C3, extend unchanged (tools/gpu_ab.sh).
-             "-ffp-contract=off", "-fno-gpu-rdc", "-munsafe-fp-atomics", "-fno-slp-vectorize",
-             "-Wno-unused-result", *extra]
+    flags = hip_flags(extra)
     # One object per source, compiled concurrently, then one link.
     import concurrent.futures
     import tempfile

@@ -1,4 +1,5 @@
-// kernels.hpp — launch interface between runtime.cpp and kernels.hip.
+// kernels.hpp — launch interface between runtime.hip and the kernel sources
+// (extend.hip, shade.hip, rounds.hip, kernels.hip and the post-process files).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -11,7 +12,7 @@ namespace ptd {
 
 struct dscene;
 
-// ShadeOrder outcome classes of a traced ray (kernels.hip).
+// ShadeOrder outcome classes of a traced ray (extend.hpp ExtendRay).
 constexpr uint32_t PT_OUTCOME_CLASSES = 5;   // hit: diffuse, metal, translucent, other material; miss
 
 // Per-slot state, SoA of 16-byte records.
@@ -22,7 +23,7 @@ struct dslots {
     float4* thr;        // throughput[4]
     float4* prob;       // probability[4]
     float* prob1;       // grey record form (non-null): the path's Probability, whose four components
-                        // are equal, as one float; prob and act are then not read (GreyRecord, kernels.hip)
+                        // are equal, as one float; prob and act are then not read (GreyRecord, path.hpp)
     float* lam;         // normalized lambda0 (a live path's Sample is always 0: StorePathVertex)
     uint2* act;         // active-shape stack (2 x u16 pairs)
     uint16_t* pos;      // per slot: position of its current ray (high byte) and of
@@ -37,7 +38,7 @@ struct dslots {
     const uint32_t* stop = nullptr;   // guarded rounds (ptRenderFrame's last rounds): set -> the launch returns
     uint32_t n;
     uint32_t tile_count;    // n / 256: one block per tile
-    // Ray order LENGTH (TileOrder, kernels.hip; include/pt_raykey.h).  All
+    // Ray order LENGTH (TileOrder, path.hpp; include/pt_raykey.h).  All
     // null / zero in OCTANT order.
     uint32_t len_order = 0;             // 1: a tile's new camera rays first, then continuing rays by length class
     const uint8_t* len_cls = nullptr;   // the scene's class per ray key (0..6); null until the table is trained
@@ -109,7 +110,7 @@ enum : uint32_t {
     PT_MATS_TEXWRAP = 128,    // some texture's atlas placement lies outside [0, 1] (host mask only: no lean kernel)
 };
 uint32_t pt_shade_mats(uint32_t scene_mats);
-// Grey record form (kernels.hip GreyRecord): the shade mask keeps every path's
+// Grey record form (path.hpp GreyRecord): the shade mask keeps every path's
 // Probability wavelength-uniform and its active-shape stack empty.
 constexpr bool pt_grey_mats(uint32_t shade_mats) { return !(shade_mats & (PT_MATS_TRANSLUCENT | PT_MATS_OPENPBR)); }
 // Record-form conversions of a renderer's live paths (between rounds):
@@ -205,7 +206,7 @@ hipError_t pt_launch_accumulate(float4* dst, const float4* src, uint64_t n, hipS
 // paths also end at surfaces.
 hipError_t pt_launch_shade(const ptd::dscene& S, const ptd::dslots& L, const ptd::dframe& F, const ptd::dparams& P,
                            uint32_t scene_mats, bool compact, hipStream_t st);
-// Class-pure shade (kernels.hip shade_classq_kernel): per-class lists of the
+// Class-pure shade (shade.hip shade_classq_kernel): per-class lists of the
 // round's positions built by class_list_kernel, each class's list CQ_SUB
 // sub-lists of pt_classq_sub_capacity words; counts: the PT_OUTCOME_CLASSES x
 // CQ_SUB counters of this round (zero at the launch), next_counts: the other

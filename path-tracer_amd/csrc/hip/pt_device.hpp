@@ -5,7 +5,7 @@
 // src/core/spectrum.glsl.inc, src/integrator/basic_scatter.glsl) under the
 // numerics convention of include/pt_fp.h.  Scene data is read through
 // 16-byte vector loads; the traversal stack lives in LDS with a global
-// spill area for depth beyond its LDS capacity (PT_EXTEND_CAP, kernels.hip).
+// spill area for depth beyond its LDS capacity (PT_EXTEND_CAP, variants.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>

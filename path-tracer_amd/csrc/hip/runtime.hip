@@ -221,7 +221,7 @@ struct pt_basic_renderer {
     uint32_t tiles_x = 0;
     ptd::dslots slots{};
     dbuf<float4> ray, hit, thr, prob;
-    dbuf<float> prob1;                  // grey record form's Probability (kernels.hip StorePathVertex)
+    dbuf<float> prob1;                  // grey record form's Probability (path.hpp StorePathVertex)
     bool grey = false;                  // the live paths are in the grey record form (slots.prob1 set)
     bool grey_blocked = false;          // some live path cannot take it (until the next Reset / state write)
     dbuf<uint32_t> grey_count;          // pt_launch_grey_check's result word
@@ -231,7 +231,7 @@ struct pt_basic_renderer {
     dbuf<float> lam;                    // lambda0 per slot (Sample is 0 between rounds)
     dbuf<float2> uv;
     dbuf<uint2> act;
-    dbuf<uint16_t> pos;                 // TileOrder positions (kernels.hip)
+    dbuf<uint16_t> pos;                 // TileOrder positions (path.hpp)
     dbuf<uint8_t> slotof;               // position -> slot within the tile
     dbuf<uint64_t> outcome;             // ShadeOrder: outcome-class bits per tile (extend -> shade)
     dbuf<uint32_t> tilecost, order;     // longest-first tile order (extend -> tile_order -> extend)
@@ -259,7 +259,7 @@ struct pt_basic_renderer {
     uint64_t rays = 0;                  // rays traced since the last Reset
     dbuf<uint32_t> spill;
     uint32_t ray_order = PT_RAY_ORDER_AUTO;   // ptSetBasicRendererRayOrder
-    dbuf<uint16_t> len_cam;             // LENGTH order: camera rays per tile (kernels.hip TileOrderLengthKey)
+    dbuf<uint16_t> len_cam;             // LENGTH order: camera rays per tile (path.hpp TileOrderLengthKey)
     bool len_cam_stale = true;          // len_cam does not describe the rays in place: zero it before a training round
 };
 
@@ -813,7 +813,7 @@ static uint32_t NodeCacheLayout(const pt_scene_packs* p, std::vector<pt_packed_m
 
 // Material types reachable by a hit (every shape's material), whether any
 // medium can scatter, whether any shape is not a mesh instance and whether sky
-// light sampling is on: selects the shade kernel instantiation (kernels.hip
+// light sampling is on: selects the shade kernel instantiation (shade.hip
 // pt_shade_mats).
 static uint32_t SceneMaterialMask(const pt_scene_packs* p)
 {
@@ -1002,7 +1002,7 @@ int ptUpdateScene(pt_device* d, pt_scene* s, const pt_scene_packs* p, uint32_t d
         D.blas_firstbits = F;
         D.stack16 = 1;
     }
-    // The LDS node cache rides with the u16 stack (kernels.hip LaunchExtendE).
+    // The LDS node cache rides with the u16 stack (variants.hpp HasNodeCache).
     D.node_cache = D.stack16 ? 2 * s->cached_pairs : 0u;
     // Extend's form: the mesh-only loop for a one-mesh scene, unless
     // ptSetSceneExtendForm asks for the general one (identical results).
@@ -1248,7 +1248,7 @@ static uint32_t ShadeMats(const pt_basic_renderer* r)
 // four-float record.
 static bool GreyForm(const pt_basic_renderer* r) { return pt_grey_mats(pt_shade_mats(ShadeMats(r))); }
 
-// The record form of the renderer's live paths (GreyRecord, kernels.hip
+// The record form of the renderer's live paths (GreyRecord, path.hpp
 // StorePathVertex): grey while the shade mask keeps every Probability
 // wavelength-uniform and every active-shape stack empty.  A mask change
 // between rounds (a scene update without Reset, ptSetBasicRendererOpenPBR)
@@ -1311,7 +1311,7 @@ int ptResetBasicRenderer(pt_device* d, pt_basic_renderer* r)
 // no spilled stack (renderer mode 1); mode 0 never fuses, mode 2 fuses
 // whenever the kernel applies (tests and A/B).
 
-// Completion queue of the shade kernel (kernels.hip ShadeTile): worth its
+// Completion queue of the shade kernel (shade.hpp ShadeTile): worth its
 // barriers when paths also end at surfaces -- sky light sampling (a sample
 // below the horizon ends the path), roulette, or metal / translucent /
 // OpenPBR BSDFs (failed samples) -- so that completions are scattered over
@@ -1416,7 +1416,7 @@ static uint32_t SplitGroups(const pt_basic_renderer* r)
     return (!RoundFused(r, L) && L.tile_count >= SPLIT_MIN_TILES) ? SPLIT_AUTO_GROUPS : 1u;
 }
 
-// Class-pure shade inside tile groups (kernels.hip shade_classq_kernel):
+// Class-pure shade inside tile groups (shade.hip shade_classq_kernel):
 // scenes with more than one material type whose shade instantiation has a
 // class-pure form.  In tile groups the lists' latency and the gathers' extra
 // bytes overlap the other groups' launches (C2 +6 %, C5 +6 %); alone on one
@@ -1435,7 +1435,7 @@ static bool ClassListRounds(const pt_basic_renderer* r) { return SplitGroups(r) 
 
 // --- ray order (ptSetBasicRendererRayOrder; DESIGN.md §4 "Length classes") ------
 // LENGTH places a tile's new rays by the traversal length their key's class
-// predicts (kernels.hip TileOrderLengthKey), from the scene's table.  It runs
+// predicts (path.hpp TileOrderLengthKey), from the scene's table.  It runs
 // where extend has a training instantiation (the mesh-only loop, no spilled
 // stack) and the tile shade a LENGTH one; elsewhere the renderer keeps OCTANT
 // and reports it.  The fused round kernels and the class-list shade place
@@ -2212,7 +2212,7 @@ int ptReadBasicRendererStreamState(pt_device* d, pt_basic_renderer* r, uint32_t 
         O.lambda0 = lam[s];
         O.throughput[0] = thr[s].x; O.throughput[1] = thr[s].y; O.throughput[2] = thr[s].z; O.throughput[3] = thr[s].w;
         O.probability[0] = prob[s].x; O.probability[1] = prob[s].y; O.probability[2] = prob[s].z; O.probability[3] = prob[s].w;
-        O.sample[0] = O.sample[1] = O.sample[2] = 0.0f;   // StorePathVertex (kernels.hip)
+        O.sample[0] = O.sample[1] = O.sample[2] = 0.0f;   // StorePathVertex (path.hpp)
         O.active01 = act[s].x;
         O.active23 = act[s].y;
     }
@@ -2232,7 +2232,7 @@ int ptReadBasicRendererState(pt_device* d, pt_basic_renderer* r, pt_pixel_state*
 // scatters (basic_trace.glsl then basic_scatter.glsl), so the next Run's
 // extend replaces it before anything reads it; until then the readback
 // reports a miss.  Sample must be 0: a live path's Sample is 0 between rounds
-// (StorePathVertex, kernels.hip).  Checked before anything is written: every
+// (StorePathVertex, path.hpp).  Checked before anything is written: every
 // active-stack entry is 0xFFFF or a shape of the scene, lambda0 lies in
 // [0, 1].
 int ptWriteBasicRendererStreamState(pt_device* d, pt_basic_renderer* r, uint32_t stream, const pt_pixel_state* in)

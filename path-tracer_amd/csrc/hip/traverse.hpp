@@ -1,6 +1,7 @@
 // traverse.hpp — Trace() on the device (scene.glsl.inc:304-611): the
-// per-lane traversal state machine shared by the extend kernel (kernels.hip)
-// and the preview kernel (preview.hip).
+// per-lane traversal state machine shared by the extend kernels (extend.hpp: extend.hip,
+// rounds.hip), the preview kernel (preview.hip) and the denoise guides
+// (denoise.hip); the hit attributes also serve shade.hpp.
 #pragma once
 
 #include "pt_device.hpp"

@@ -1,6 +1,6 @@
 """GPU: the host-proved shade specialisations, on scenes that pass and on
 scenes that FAIL each gate.  The host picks the shade
-instantiation from the packs (runtime.hip SceneMaterialMask, kernels.hip
+instantiation from the packs (runtime.hip SceneMaterialMask, shade.hip
 pt_shade_mats); a wrong gate would silently run a kernel that drops terms the
 scene needs.  Each case asserts which variant ran (ptGetBasicRendererShadeInfo)
 and that the render is bit-exact against the oracle.

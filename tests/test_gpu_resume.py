@@ -1,5 +1,5 @@
 """GPU: bit-exact resume of a render (SURVEY.md §5 checkpoint/resume row) and
-the grey path-record form's switches (kernels.hip StorePathVertex), all
+the grey path-record form's switches (path.hpp StorePathVertex), all
 through libpathtracer.so against uninterrupted renders and the CPU oracle.
 
 Resume = the live paths (ptWriteBasicRendererState: next ray + path record,

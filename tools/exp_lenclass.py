@@ -12,7 +12,7 @@ length (DESIGN.md §4 "Length classes").  CPU only.
    8^3 over the TLAS root's box x octahedral direction 8^2) over the continuing
    rays of the rounds before the last; 7 classes at the count-weighted 1/7 ..
    6/7 quantiles of the means, the middle class for keys without a sample --
-   what kernels.hip length_classes_kernel computes.
+   what extend.hip length_classes_kernel computes.
 3. Orders of the last round's 16x16 tiles (four 64-lane waves; rays keep pixel
    order within a key): pixel order; direction octant (OCTANT); camera rays
    first, then octant; camera rays first, then length class (LENGTH); true

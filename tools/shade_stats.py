@@ -5,7 +5,7 @@ Needs the experiment build:  python tools/build_variant.py shadestats -DPT_SHADE
 usage (GPU box):  python tools/shade_stats.py OUT.json [CONFIG ...]
 
 For each config: Reset, Run(2), SETTLE rounds, then the counters of ROUNDS
-shade launches.  Per mark k (kernels.hip SM_*): waves = wave executions that
+shade launches.  Per mark k (bsdf.hpp SM_*): waves = wave executions that
 reached it, lanes = active lanes summed over them; lanes / waves = the mark's
 mean SIMD occupancy (of 64), waves / waves(entry) = how often a wave runs it.
 """
