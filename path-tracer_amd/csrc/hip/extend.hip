@@ -155,7 +155,7 @@ __global__ __launch_bounds__(256) void extend_stats_kernel(dscene S, Src src, ui
 
 }  // namespace ptd
 
-// --- launchers (called from runtime.hip) -----------------------------------------
+// --- launchers (called from rt_rounds.hip and rt_probe.hip) ----------------------
 
 using ptv::Blocks;
 

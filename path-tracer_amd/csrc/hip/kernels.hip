@@ -184,7 +184,7 @@ __global__ __launch_bounds__(256) void xdiv_check_kernel(uint64_t n, uint32_t se
 
 }  // namespace ptd
 
-// --- launchers (called from runtime.hip) -----------------------------------------
+// --- launchers (called from the rt_*.hip host files) -----------------------------
 
 using ptv::Blocks;
 

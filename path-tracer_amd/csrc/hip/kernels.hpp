@@ -1,4 +1,4 @@
-// kernels.hpp — launch interface between runtime.hip and the kernel sources
+// kernels.hpp — launch interface between the host files (rt_*.hip) and the kernel sources
 // (extend.hip, shade.hip, rounds.hip, kernels.hip and the post-process files).
 #pragma once
 

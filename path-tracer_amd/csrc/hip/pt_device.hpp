@@ -18,7 +18,7 @@ namespace ptd {
 
 constexpr uint32_t SHAPE_INDEX_NONE = 0xFFFFFFFFu;
 constexpr uint32_t TEXTURE_INDEX_NONE = 0xFFFFFFFFu;
-constexpr uint32_t PT_SHAPE_FLAG_UV = 1u;   // pt_packed_shape::Pad0 on the device (runtime.hip)
+constexpr uint32_t PT_SHAPE_FLAG_UV = 1u;   // pt_packed_shape::Pad0 on the device (rt_scene.hip)
 
 // Device view of the packed scene (the 11 descriptor bindings of
 // scene.glsl.inc:121-179).
@@ -49,9 +49,9 @@ struct dscene {
     float vmf_inv_kappa, vmf_exp_m2k, vmf_norm;   // VmfConstants(g.SkyboxConcentration), set on upload
     float sky_flat;                // SampleParametricSpectrum((0, 0, 100), L) for any finite L (SkyFlat)
     uint32_t node_cache;           // BLAS nodes [0, node_cache) are the top child pairs the extend kernel
-                                   // keeps in LDS (NodeCacheLayout, runtime.hip); 0: no cache
+                                   // keeps in LDS (NodeCacheLayout, rt_scene.hip); 0: no cache
     // One-mesh scenes (ShapeCount == 1, the TLAS root a leaf, shape 0 a mesh
-    // instance; classified at upload, runtime.hip): extend runs the mesh-only
+    // instance; classified at upload, rt_scene.hip): extend runs the mesh-only
     // loop (traverse.hpp MeshStep) and reads what its prologue needs of the
     // shape and of the mesh root from these kernel arguments (scalar loads)
     // instead of through three dependent per-lane loads.

@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256, ShadeMinWaves<MATS>()) void rounds_kernel(
 
 }  // namespace ptd
 
-// --- launchers (called from runtime.hip) -----------------------------------------
+// --- launchers (called from rt_rounds.hip) ---------------------------------------
 
 // The default extend variant's LDS stack without spill, one instantiation of
 // each kernel per shade material mask and stack entry width.  batch: the

@@ -1,0 +1,221 @@
+// rt_probe.hip — host side of libpathtracer.so: the test probes: ray queries, traversal
+// counters, device numerics and the texture sampler, each checked against the
+// host by the tests.
+#include "runtime.hpp"
+
+using namespace ptrt;
+
+extern "C" {
+
+int ptTraceRays(pt_device* d, pt_scene* s, uint32_t n, const float* origins, const uint32_t* vel, const float* dur,
+                pt_hit_record* out)
+{
+    if (!d || !s || (n && (!origins || !vel || !dur || !out))) { SetError("null argument"); return -1; }
+    if (!s->valid) { SetError("scene has no valid packs"); return -1; }
+    if (n == 0) return 0;
+    PT_HIP(hipSetDevice(d->id));
+    bool spill = s->stack_needed > pt_extend_stack_cap();
+    dbuf<float> d_o, d_t;
+    dbuf<uint32_t> d_v, d_spill;
+    dbuf<float4> d_hit, d_rec;
+    dbuf<float2> d_hc, d_uv;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = d_o.upload(origins, (size_t)n * 3)) != hipSuccess) break;
+        if ((e = d_t.upload(dur, n)) != hipSuccess) break;
+        if ((e = d_v.upload(vel, n)) != hipSuccess) break;
+        if ((e = d_hit.alloc(n)) != hipSuccess || (e = d_rec.alloc(n)) != hipSuccess) break;
+        if ((e = d_hc.alloc(n)) != hipSuccess || (e = d_uv.alloc(n)) != hipSuccess) break;
+        if (spill && (e = d_spill.alloc((size_t)(s->stack_needed - pt_extend_stack_cap()) * n)) != hipSuccess) break;
+        e = pt_launch_trace_rays(s->d, n, d_o.ptr, d_v.ptr, d_t.ptr, d_hit.ptr, d_hc.ptr, d_rec.ptr, d_uv.ptr,
+                                 spill ? d_spill.ptr : nullptr, d->stream);
+        if (e != hipSuccess) break;
+        if ((e = hipStreamSynchronize(d->stream)) != hipSuccess) break;
+        std::vector<float4> rec(n);
+        std::vector<float2> uv(n);
+        if ((e = hipMemcpy(rec.data(), d_rec.ptr, (size_t)n * 16, hipMemcpyDeviceToHost)) != hipSuccess) break;
+        if ((e = hipMemcpy(uv.data(), d_uv.ptr, (size_t)n * 8, hipMemcpyDeviceToHost)) != hipSuccess) break;
+        for (uint32_t i = 0; i < n; i++) {
+            std::memcpy(&out[i].time, &rec[i].x, 4);
+            std::memcpy(&out[i].shape_material, &rec[i].y, 4);
+            std::memcpy(&out[i].packed_normal, &rec[i].z, 4);
+            std::memcpy(&out[i].packed_tangent, &rec[i].w, 4);
+            out[i].u = uv[i].x;
+            out[i].v = uv[i].y;
+        }
+    } while (0);
+    if (e != hipSuccess) { SetError("ptTraceRays: %s", hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
+// Diagnostic: ptExtendStats's traversal counters for caller-given rays (the
+// ptTraceRays inputs), plus each ray's step count (order-independent: a ray's
+// traversal does not depend on its neighbours).
+int ptTraceRaysStats(pt_device* d, pt_scene* s, uint32_t n, const float* origins, const uint32_t* vel,
+                     const float* dur, uint64_t out[PT_EXTEND_STATS_COUNT], uint32_t* steps)
+{
+    if (!d || !s || !out || (n && (!origins || !vel || !dur))) { SetError("null argument"); return -1; }
+    if (!s->valid) { SetError("scene has no valid packs"); return -1; }
+    for (int i = 0; i < PT_EXTEND_STATS_COUNT; i++) out[i] = 0;
+    if (n == 0) return 0;
+    PT_HIP(hipSetDevice(d->id));
+    bool spill = s->stack_needed > pt_extend_stack_cap();
+    dbuf<float> d_o, d_t;
+    dbuf<uint32_t> d_v, d_spill, d_steps;
+    dbuf<float4> d_hit;
+    dbuf<float2> d_hc;
+    dbuf<unsigned long long> d_out;
+    hipError_t e = hipSuccess;
+    unsigned long long h[PT_EXTEND_STATS_COUNT] = {};
+    do {
+        if ((e = d_o.upload(origins, (size_t)n * 3)) != hipSuccess) break;
+        if ((e = d_t.upload(dur, n)) != hipSuccess) break;
+        if ((e = d_v.upload(vel, n)) != hipSuccess) break;
+        if ((e = d_hit.alloc(n)) != hipSuccess || (e = d_hc.alloc(n)) != hipSuccess) break;
+        if ((e = d_out.alloc(PT_EXTEND_STATS_COUNT)) != hipSuccess) break;
+        if (steps && (e = d_steps.alloc(n)) != hipSuccess) break;
+        if (spill && (e = d_spill.alloc((size_t)(s->stack_needed - pt_extend_stack_cap()) * n)) != hipSuccess) break;
+        if ((e = hipMemsetAsync(d_out.ptr, 0, sizeof(h), d->stream)) != hipSuccess) break;
+        e = pt_launch_trace_rays_stats(s->d, n, d_o.ptr, d_v.ptr, d_t.ptr, d_hit.ptr, d_hc.ptr,
+                                       spill ? d_spill.ptr : nullptr, d_out.ptr, steps ? d_steps.ptr : nullptr,
+                                       d->stream);
+        if (e != hipSuccess) break;
+        if ((e = hipMemcpyAsync(h, d_out.ptr, sizeof(h), hipMemcpyDeviceToHost, d->stream)) != hipSuccess) break;
+        if (steps && (e = hipMemcpyAsync(steps, d_steps.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, d->stream)) != hipSuccess)
+            break;
+        e = hipStreamSynchronize(d->stream);
+    } while (0);
+    if (e != hipSuccess) { SetError("ptTraceRaysStats: %s", hipGetErrorString(e)); return (int)e; }
+    for (int i = 0; i < PT_EXTEND_STATS_COUNT; i++) out[i] = h[i];
+    return 0;
+}
+
+int ptCheckFastDivision(pt_device* d, uint64_t n, uint32_t seed, uint64_t* mismatches)
+{
+    if (!d || !mismatches) { SetError("null argument"); return -1; }
+    PT_HIP(hipSetDevice(d->id));
+    unsigned long long* dm = nullptr;
+    PT_HIP(hipMalloc(&dm, sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(dm, 0, sizeof(unsigned long long), d->stream);
+    if (e == hipSuccess) e = pt_launch_xdiv_check(n, seed, dm, d->stream);
+    unsigned long long h = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, dm, sizeof(h), hipMemcpyDeviceToHost, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    (void)hipFree(dm);
+    if (e != hipSuccess) { SetError("ptCheckFastDivision: %s", hipGetErrorString(e)); return (int)e; }
+    *mismatches = h;
+    return 0;
+}
+
+int ptCheckFastReciprocal(pt_device* d, uint64_t* mismatches)
+{
+    if (!d || !mismatches) { SetError("null argument"); return -1; }
+    PT_HIP(hipSetDevice(d->id));
+    unsigned long long* dm = nullptr;
+    PT_HIP(hipMalloc(&dm, sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(dm, 0, sizeof(unsigned long long), d->stream);
+    if (e == hipSuccess) e = pt_launch_rcp_check(dm, d->stream);
+    unsigned long long h = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, dm, sizeof(h), hipMemcpyDeviceToHost, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    (void)hipFree(dm);
+    if (e != hipSuccess) { SetError("ptCheckFastReciprocal: %s", hipGetErrorString(e)); return (int)e; }
+    *mismatches = h;
+    return 0;
+}
+
+int ptEvalNumerics(pt_device* d, uint32_t op, uint32_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c,
+                   uint32_t* out)
+{
+    if (!d) { SetError("null argument"); return -1; }
+    const uint32_t operands = pt_numerics_operands(op), outputs = pt_numerics_outputs(op);
+    if (operands == 0) { SetError("ptEvalNumerics: unknown op %u", op); return -1; }
+    if (n && (!out || !a || (operands > 1 && !b) || (operands > 2 && !c))) { SetError("null argument"); return -1; }
+    if (n == 0) return 0;
+    PT_HIP(hipSetDevice(d->id));
+    dbuf<uint32_t> d_a, d_b, d_c, d_out;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = d_a.upload(a, n)) != hipSuccess) break;
+        if (operands > 1 && (e = d_b.upload(b, n)) != hipSuccess) break;
+        if (operands > 2 && (e = d_c.upload(c, n)) != hipSuccess) break;
+        if ((e = d_out.alloc((size_t)n * outputs)) != hipSuccess) break;
+        if ((e = pt_launch_numerics_probe(op, n, d_a.ptr, d_b.ptr, d_c.ptr, d_out.ptr, d->stream)) != hipSuccess) break;
+        if ((e = hipStreamSynchronize(d->stream)) != hipSuccess) break;
+        e = hipMemcpy(out, d_out.ptr, (size_t)n * outputs * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    } while (0);
+    if (e != hipSuccess) { SetError("ptEvalNumerics: %s", hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
+int ptSampleTextures(pt_device* d, pt_scene* s, uint32_t n, const uint32_t* texture_index, const float* uv,
+                     uint32_t wrap, float* rgba)
+{
+    if (!d || !s || (n && (!texture_index || !uv || !rgba))) { SetError("null argument"); return -1; }
+    if (s->dev != d) { SetError("ptSampleTextures: scene of another device"); return -1; }
+    if (!s->valid) { SetError("scene has no valid packs"); return -1; }
+    if (wrap > 1) { SetError("ptSampleTextures: wrap %u", wrap); return -1; }
+    if (wrap == 1 && (s->mats & PT_MATS_TEXWRAP)) {
+        SetError("ptSampleTextures: the two-select wrap needs every atlas placement inside [0, 1]");
+        return -1;
+    }
+    for (uint32_t i = 0; i < n; i++)
+        if (texture_index[i] >= s->texture_count) {
+            SetError("ptSampleTextures: texture index %u >= texture count %u", texture_index[i], s->texture_count);
+            return -1;
+        }
+    if (n == 0) return 0;
+    PT_HIP(hipSetDevice(d->id));
+    dbuf<uint32_t> d_index;
+    dbuf<float2> d_uv;
+    dbuf<float4> d_rgba;
+    hipError_t e = hipSuccess;
+    do {
+        if ((e = d_index.upload(texture_index, n)) != hipSuccess) break;
+        if ((e = d_uv.upload(reinterpret_cast<const float2*>(uv), n)) != hipSuccess) break;
+        if ((e = d_rgba.alloc(n)) != hipSuccess) break;
+        if ((e = pt_launch_sample_textures(s->d, n, d_index.ptr, d_uv.ptr, wrap == 1, d_rgba.ptr, d->stream)) != hipSuccess)
+            break;
+        if ((e = hipStreamSynchronize(d->stream)) != hipSuccess) break;
+        e = hipMemcpy(rgba, d_rgba.ptr, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost);
+    } while (0);
+    if (e != hipSuccess) { SetError("ptSampleTextures: %s", hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
+static int ExtendStats(pt_device* d, pt_basic_renderer* r, uint64_t* out, uint32_t* steps_out, const char* what)
+{
+    if (!d || (!out && !steps_out)) { SetError("null argument"); return -1; }
+    if (CheckReady(r) != 0) return -1;
+    PT_HIP(hipSetDevice(d->id));
+    if (int e = EnsureSpill(r)) return e;
+    unsigned long long* dm = nullptr;
+    uint32_t* ds = nullptr;
+    PT_HIP(hipMalloc(&dm, PT_EXTEND_STATS_COUNT * sizeof(unsigned long long)));
+    hipError_t e = steps_out ? hipMalloc(&ds, (size_t)r->slots.n * 4) : hipSuccess;
+    if (e == hipSuccess) e = hipMemsetAsync(dm, 0, PT_EXTEND_STATS_COUNT * sizeof(unsigned long long), d->stream);
+    if (e == hipSuccess)
+        e = pt_launch_extend_stats(r->scene->d, r->slots, Frame(r), r->slots.spill, dm, ds, d->stream);
+    unsigned long long h[PT_EXTEND_STATS_COUNT] = {};
+    if (e == hipSuccess) e = hipMemcpyAsync(h, dm, sizeof(h), hipMemcpyDeviceToHost, d->stream);
+    if (e == hipSuccess && ds) e = hipMemcpyAsync(steps_out, ds, (size_t)r->slots.n * 4, hipMemcpyDeviceToHost, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    (void)hipFree(dm);
+    if (ds) (void)hipFree(ds);
+    if (e != hipSuccess) { SetError("%s: %s", what, hipGetErrorString(e)); return (int)e; }
+    if (out)
+        for (int i = 0; i < PT_EXTEND_STATS_COUNT; i++) out[i] = h[i];
+    return 0;
+}
+
+int ptExtendStats(pt_device* d, pt_basic_renderer* r, uint64_t out[PT_EXTEND_STATS_COUNT])
+{
+    return ExtendStats(d, r, out, nullptr, "ptExtendStats");
+}
+
+int ptExtendStepCounts(pt_device* d, pt_basic_renderer* r, uint32_t* steps)
+{
+    return ExtendStats(d, r, nullptr, steps, "ptExtendStepCounts");
+}
+
+}  // extern "C"

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256, ShadeMinWaves<MATS>()) void shade_kernel(dscen
 // A new ray stays at the position it replaces: TileOrder needs a tile's 256
 // new rays together, which a class-pure block does not hold; the slot <->
 // position map is unchanged, so the results are identical.  Used inside tile
-// groups (runtime.hip ClassLists), where the lists' latency and the gathers'
+// groups (rt_rounds.hip ClassLists), where the lists' latency and the gathers'
 // extra bytes overlap the other groups' launches: C2 +6 %, C5 +6 %; on one
 // stream the lists cost more than the lanes gain.
 //
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256, ShadeMinWaves<MATS>()) void shade_classq_kerne
 
 }  // namespace ptd
 
-// --- launchers (called from runtime.hip) -----------------------------------------
+// --- launchers (called from rt_rounds.hip; finalize from rt_renderer.hip) --------
 
 using ptv::Blocks;
 

@@ -200,7 +200,7 @@ PT_DEV void CompletionQueue(const dscene& S, const dslots& L, const dframe& F, c
 
 // One tile of shade (basic_scatter.glsl:main for the tile's 256 slots).
 // COMPACT: completion queue, for scenes whose paths also end at surfaces
-// (ShadeCompact, runtime.hip).
+// (ShadeCompact, rt_rounds.hip).
 // LEN: the tile's new rays in LENGTH order (TileOrderLengthKey).
 template <uint32_t MATS, bool COMPACT = false, bool LEN = false>
 PT_DEV void ShadeTile(const dscene& S, const dslots& L, const dframe& F, const dparams& Pm, uint32_t tile)

@@ -31,7 +31,7 @@
 //
 // The minima are kept as the complement of the bit pattern and raised with
 // atomicMax, so that the all-zero struct the runtime clears is "no value
-// yet" for all four; the runtime turns them back (runtime.hip).
+// yet" for all four; the runtime turns them back (rt_post.hip).
 #include "pt_device.hpp"
 #include "kernels.hpp"
 #include "../../../include/pt_stats.h"

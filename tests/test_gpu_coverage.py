@@ -739,7 +739,7 @@ def test_whole_1024spp_frame_bit_exact(pt, dev):
 
 
 def test_comm_deadline_aborts_and_device_recovers(pt, dev):
-    """The wait's deadline branch with a live RCCL communicator (runtime.hip
+    """The wait's deadline branch with a live RCCL communicator (rt_device.hip
     DeviceWait): with a 1 ms deadline, waiting on 150 queued
     full-size C3 rounds (~60 ms) gives up with PT_ERROR_TIMEOUT and aborts the
     communicator (ncclCommAbort); exchanges on it then fail with

@@ -1,4 +1,4 @@
-"""GPU: ptRenderFrame's read-back schedule (runtime.hip: the first batch
+"""GPU: ptRenderFrame's read-back schedule (rt_rounds.hip: the first batch
 after Run(2) without a read-back, the last rounds guarded on the device).
 Whatever the schedule, a frame is Reset, Run(2), then Run(1) rounds until the
 completed paths reach the target or max_rounds rounds ran

@@ -1,6 +1,6 @@
 """GPU: the host-proved shade specialisations, on scenes that pass and on
 scenes that FAIL each gate.  The host picks the shade
-instantiation from the packs (runtime.hip SceneMaterialMask, shade.hip
+instantiation from the packs (rt_scene.hip SceneMaterialMask, shade.hip
 pt_shade_mats); a wrong gate would silently run a kernel that drops terms the
 scene needs.  Each case asserts which variant ran (ptGetBasicRendererShadeInfo)
 and that the render is bit-exact against the oracle.
@@ -209,7 +209,7 @@ def test_config_variants(pt, dev, config, grey):
 
 def test_node_cache_layout_is_result_neutral(pt, dev):
     """The LDS node cache's device BVH layout (the top child pairs first,
-    every index remapped; runtime.hip NodeCacheLayout): on for the u16-stack
+    every index remapped; rt_scene.hip NodeCacheLayout): on for the u16-stack
     scenes, off when the stack needs 32-bit entries, and the same hits and
     frames either way -- against the oracle, which traverses the packs'
     original numbering."""

@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 AUTO, OCTANT, LENGTH = 0, 1, 2   # PT_RAY_ORDER_*
 FLAGS = 3                        # ACCUMULATE | SAMPLE_JITTER
-TRAIN_FIRST = 16                 # the first LENGTH rounds after a clear train (runtime.hip)
+TRAIN_FIRST = 16                 # the first LENGTH rounds after a clear train (rt_rounds.hip)
 
 
 @pytest.fixture(scope="module")
