@@ -1,0 +1,208 @@
+"""The device, the device copy of a scene and the communicator
+(libpathtracer.so; include/pt_api.h)."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import TYPE_CHECKING
+
+import numpy as np
+
+from . import _native as N
+from ._core import U32, U64, F64, Handle, extend_stats, hip, hip_get
+
+if TYPE_CHECKING:
+    from .frame import SampleBuffer
+
+
+def device_count() -> int:
+    n = C.c_int(0)
+    N.hip_lib().ptGetDeviceCount(C.byref(n))
+    return n.value
+
+
+class Device(Handle):
+    """A HIP device + stream (replaces the reference's `vulkan` context)."""
+
+    _destroy, _destroy_takes_device = "ptDestroyDevice", False
+
+    def __init__(self, hip_device: int = 0):
+        self._create("ptCreateDevice", int(hip_device))
+        self.index = hip_device
+
+    def synchronize(self):
+        hip("ptSynchronize", self._h)
+
+    def set_profiling(self, enable: bool, period: int = 1):
+        """Kernel timing with HIP events; period > 1 times every period-th round only."""
+        hip("ptSetProfiling", self._h, int(enable))
+        hip("ptSetProfilingPeriod", self._h, int(period))
+
+    def kernel_stats(self, kernel: int):
+        return hip_get("ptGetKernelStats", self._h, kernel, types=(U64, F64))
+
+    def kernel_rounds(self, kernel: int) -> int:
+        """Rounds covered by the timed launches of `kernel` (a round batch
+        covers several): total_ms / rounds is its time per round."""
+        return hip_get("ptGetKernelRounds", self._h, kernel, types=(U64,))
+
+    def reset_kernel_stats(self):
+        hip("ptResetKernelStats", self._h)
+
+    def set_statistics_variant(self, variant: int):
+        """STATS_VARIANT_AUTO / _PLAIN / _UNIFORM: the statistics kernel's
+        histogram update (identical results; ptSetFrameStatisticsVariant)."""
+        hip("ptSetFrameStatisticsVariant", self._h, int(variant))
+
+    def check_fast_division(self, n: int, seed: int = 1) -> int:
+        return hip_get("ptCheckFastDivision", self._h, n, seed, types=(U64,))
+
+    def check_fast_reciprocal(self) -> int:
+        return hip_get("ptCheckFastReciprocal", self._h, types=(U64,))
+
+    def eval_numerics(self, op, a, b=None, c=None) -> np.ndarray:
+        """Test probe (ptEvalNumerics): operation `op` (a name of
+        N.NUMERICS_OPS or its id) on the device over uint32 operand words
+        (float bit patterns or integers).  Returns the result words, shape
+        (n,) or (n, outputs) for an op with several."""
+        name = N.NUMERICS_OPS[op] if isinstance(op, int) else op
+        arrays = [None if x is None else np.ascontiguousarray(x, dtype=np.uint32).reshape(-1) for x in (a, b, c)]
+        n = len(arrays[0])
+        outputs = N.NUMERICS_OUTPUTS.get(name, 1)
+        out = np.zeros(n * outputs, dtype=np.uint32)
+        ptrs = [None if x is None else N.u32ptr(x) for x in arrays]
+        hip("ptEvalNumerics", self._h, N.NUMERICS_OPS.index(name), n, *ptrs, N.u32ptr(out))
+        return out if outputs == 1 else out.reshape(n, outputs)
+
+
+def _records(pointer, count: int, dtype: np.dtype) -> np.ndarray:
+    """A copy of `count` packed records at `pointer` (none for a null pointer)."""
+    if not (count and pointer):
+        return np.zeros(0, dtype=dtype)
+    return np.frombuffer((C.c_char * (count * dtype.itemsize)).from_address(pointer), dtype=dtype).copy()
+
+
+def _ray_batch(origins, packed_velocities, durations):
+    """(origins (n, 3), packed velocities (n,), durations (n,)) as the trace entry points read them."""
+    return (np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3),
+            np.ascontiguousarray(packed_velocities, dtype=np.uint32).reshape(-1),
+            np.ascontiguousarray(durations, dtype=np.float32).reshape(-1))
+
+
+class DeviceScene(Handle):
+    """Device copy of a packed scene (CreateVulkanScene / UpdateVulkanScene)."""
+
+    _destroy = "ptDestroyScene"
+
+    def __init__(self, device: Device):
+        self.device = device
+        self.cameras = np.zeros(0, dtype=N.CAMERA_DTYPE)
+        self.shapes = np.zeros(0, dtype=N.SHAPE_DTYPE)
+        self._create("ptCreateScene", device.handle)
+
+    def set_stack_format(self, fmt: int):
+        """PT_STACK_FORMAT_* (0 auto, 1 packed 32-bit words, 2 node indices); next update()."""
+        hip("ptSetSceneStackFormat", self._h, int(fmt))
+
+    def set_hit_record_form(self, form: int):
+        """PT_HIT_RECORD_* (0 auto, 1 face index); next update()."""
+        hip("ptSetSceneHitRecordForm", self._h, int(form))
+
+    def set_extend_form(self, form: int):
+        """PT_EXTEND_FORM_* (0 auto, 1 general traversal loop); next update()."""
+        hip("ptSetSceneExtendForm", self._h, int(form))
+
+    @property
+    def extend_form(self) -> int:
+        """The extend form the uploaded scene runs: 1 general, 2 mesh-only (ptGetSceneExtendForm)."""
+        return hip_get("ptGetSceneExtendForm", self._h)
+
+    def update(self, scene, dirty_flags: int = 0xFFFFFFFF):
+        packs = scene.packs() if hasattr(scene, "packs") else scene
+        hip("ptUpdateScene", self.device.handle, self._h, C.byref(packs), dirty_flags)
+        # The packed camera records as uploaded (FrameHistory keeps a frame's own).
+        self.cameras = _records(packs.cameras, packs.camera_count, N.CAMERA_DTYPE)
+        # And the packed shapes (FrameHistory(follow_shapes=True) compares two frames' transforms).
+        self.shapes = _records(packs.shapes, packs.shape_count, N.SHAPE_DTYPE)
+
+    def length_table(self) -> dict:
+        """{classes, trained, rounds}: the scene's traversal-length table, one
+        class 0..6 per ray key, whether it was trained since the last clear and
+        the LENGTH rounds counted since then (diagnostic, ptReadSceneLengthTable)."""
+        cls = np.zeros(N.RAYKEY_COUNT, dtype=np.uint8)
+        t, n = hip_get("ptReadSceneLengthTable", self.device.handle, self._h, cls.ctypes.data, types=(U32, U64))
+        return {"classes": cls, "trained": bool(t), "rounds": n}
+
+    @property
+    def stack_needed(self) -> int:
+        """Traversal stack entries the uploaded scene can need (TLAS + BLAS depth)."""
+        return hip_get("ptSceneStackNeeded", self._h)
+
+    @property
+    def node_cache_pairs(self) -> int:
+        """BLAS child pairs the extend kernel keeps in LDS (0: none; ptSceneNodeCache)."""
+        return hip_get("ptSceneNodeCache", self._h)
+
+    def trace_rays(self, origins: np.ndarray, packed_velocities: np.ndarray, durations: np.ndarray) -> np.ndarray:
+        """Bit-exact Trace() of a ray batch (scene.glsl.inc:522-611)."""
+        o, v, d = _ray_batch(origins, packed_velocities, durations)
+        out = np.zeros(len(v), dtype=N.HIT_RECORD_DTYPE)
+        hip("ptTraceRays", self.device.handle, self._h, len(v), N.fptr(o), N.u32ptr(v), N.fptr(d), out.ctypes.data)
+        return out
+
+    def sample_textures(self, texture_index: np.ndarray, uv: np.ndarray, wrap: int = 0) -> np.ndarray:
+        """Test probe (ptSampleTextures): SampleTexture of the uploaded scene
+        at (n, 2) UVs; wrap 0 = remainder, 1 = the lean kernel's two-select
+        form (refused when a placement leaves [0, 1]).  Returns (n, 4)."""
+        t = np.ascontiguousarray(texture_index, dtype=np.uint32).reshape(-1)
+        u = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 2)
+        assert len(u) == len(t)
+        out = np.zeros((len(t), 4), dtype=np.float32)
+        hip("ptSampleTextures", self.device.handle, self._h, len(t), N.u32ptr(t), N.fptr(u), int(wrap), N.fptr(out))
+        return out
+
+    def trace_rays_stats(self, origins: np.ndarray, packed_velocities: np.ndarray, durations: np.ndarray):
+        """Traversal counters (ptExtendStats keys) and per-ray step counts of a
+        ray batch (diagnostic, ptTraceRaysStats)."""
+        o, v, d = _ray_batch(origins, packed_velocities, durations)
+        out = (C.c_uint64 * 14)()
+        steps = np.zeros(len(v), dtype=np.uint32)
+        hip("ptTraceRaysStats", self.device.handle, self._h, len(v), N.fptr(o), N.u32ptr(v), N.fptr(d), out,
+            steps.ctypes.data)
+        return extend_stats(out, 9), steps
+
+
+class Comm(Handle):
+    """RCCL communicator (one process per GPU) for the frame-end reduce."""
+
+    _destroy, _destroy_takes_device = "ptCommDestroy", False
+
+    def __init__(self, device: Device, nranks: int, rank: int, unique_id: bytes):
+        buf = (C.c_uint8 * 128)(*unique_id)
+        self.device = device
+        self._create("ptCommCreate", device.handle, nranks, rank, buf)
+
+    def set_timeout(self, seconds: float):
+        """Deadline of a device-stream wait while this communicator is live
+        (ptCommSetTimeout; default 600 s).  Past it the communicators are
+        aborted and the waiting call raises (PT_ERROR_TIMEOUT)."""
+        hip("ptCommSetTimeout", self._h, float(seconds))
+
+    @staticmethod
+    def unique_id() -> bytes:
+        buf = (C.c_uint8 * 128)()
+        hip("ptCommGetUniqueId", buf)
+        return bytes(buf)
+
+    def reduce_sample_buffer(self, sample_buffer: SampleBuffer, root: int = 0):
+        hip("ptCommReduceSampleBuffer", self.device.handle, self._h, sample_buffer.handle, root)
+
+    def reduce_sample_buffer_into(self, sample_buffer: SampleBuffer, total: SampleBuffer | None, root: int = 0):
+        """Sample sharding: `total` on `root` = sum over ranks of their own
+        accumulators (ptCommReduceSampleBufferInto); `total` may be None
+        on the other ranks."""
+        hip("ptCommReduceSampleBufferInto", self.device.handle, self._h, sample_buffer.handle,
+            total.handle if total is not None else None, root)
+
+    def gather_sample_buffer(self, sample_buffer: SampleBuffer, root: int = 0):
+        """Each rank's own bands, point-to-point to `root` (1/N of the reduce's traffic)."""
+        hip("ptCommGatherSampleBuffer", self.device.handle, self._h, sample_buffer.handle, root)

@@ -1,0 +1,237 @@
+"""What runs in libptscene.so and needs no GPU: the frame and tile
+statistics and the post-processing passes on saved accumulators, each the
+implementation its device pass equals bit for bit (include/pt_scene.h)."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+from ._core import camera_struct, guide_image, image, image_like, motion_table, pts, tile_grid
+from .params import DenoiseParameters, DenoisePairParameters, DespikeParameters, RectifyParameters, ReprojectParameters
+
+
+class FrameStatistics:
+    """pt_frame_statistics (pt_packed.h): pixel classes,
+    a 256-bin quarter-octave luminance histogram, luminance and sample-count
+    range and, from a pair of half renders, the histogram of the relative
+    half-difference r = |Y_A - Y_B| / (Y_A + Y_B).  Every field is an
+    attribute (the histograms as uint32 arrays); the methods are pt_stats.h's
+    double helpers, evaluated by libptscene.so."""
+
+    _COUNTS = ("pixels", "filled", "empty", "nonfinite", "dark", "noise_pixels", "noise_skipped")
+    _FLOATS = ("min_luminance", "max_luminance", "min_samples", "max_samples")
+    _HISTOGRAMS = ("luminance_histogram", "noise_histogram")
+
+    def __init__(self, struct: N.pt_frame_statistics):
+        self._s = struct
+        for f in self._COUNTS:
+            setattr(self, f, int(getattr(struct, f)))
+        for f in self._FLOATS:
+            setattr(self, f, np.float32(getattr(struct, f)))
+        for f in self._HISTOGRAMS:
+            setattr(self, f, np.ctypeslib.as_array(getattr(struct, f)).astype(np.uint32))
+
+    def as_struct(self) -> N.pt_frame_statistics:
+        return self._s
+
+    def tobytes(self) -> bytes:
+        return bytes(self._s)
+
+    def _histogram(self, which: str):
+        return self._s.noise_histogram if which == "noise" else self._s.luminance_histogram
+
+    def percentile(self, q: float, which: str = "luminance") -> int:
+        """The smallest bin whose cumulative count reaches ceil(q * total) of
+        the luminance (or "noise") histogram; -1 when it is empty."""
+        return int(N.scene_lib().ptsStatsPercentileBin(self._histogram(which), float(q)))
+
+    def log_average(self, q_lo: float = 0.01, q_hi: float = 0.99, which: str = "luminance") -> float:
+        """Geometric mean of the bin centres between two percentile bins (0 when empty)."""
+        return float(N.scene_lib().ptsStatsLogAverage(self._histogram(which), float(q_lo), float(q_hi)))
+
+    def auto_brightness(self, key: float = 0.18, q_lo: float = 0.01, q_hi: float = 0.99) -> float:
+        """key / log_average: ResolveParameters.Brightness is a linear scale
+        in front of the tone curve.  1 for a frame without a binned pixel."""
+        return float(N.scene_lib().ptsStatsAutoBrightness(C.byref(self._s), float(key), float(q_lo), float(q_hi)))
+
+    def noise(self, q: float = 0.95) -> float:
+        """An upper bound of the relative noise of a share q of the pair
+        pixels: the upper edge of the noise histogram's percentile bin
+        (inf without a pair pixel)."""
+        return float(N.scene_lib().ptsStatsNoise(C.byref(self._s), float(q)))
+
+    @staticmethod
+    def bin_edges() -> np.ndarray:
+        """The 257 bin edges (float64): bin b is [edges[b], edges[b + 1])."""
+        L = N.scene_lib()
+        return np.array([L.ptsStatsBinEdge(b) for b in range(N.STATS_BINS + 1)], dtype=np.float64)
+
+    def __eq__(self, other):
+        return isinstance(other, FrameStatistics) and self.tobytes() == other.tobytes()
+
+    def __repr__(self):
+        return (f"FrameStatistics(pixels={self.pixels}, filled={self.filled}, empty={self.empty}, "
+                f"nonfinite={self.nonfinite}, dark={self.dark}, luminance=[{self.min_luminance}, "
+                f"{self.max_luminance}], samples=[{self.min_samples}, {self.max_samples}], "
+                f"noise_pixels={self.noise_pixels}, noise_skipped={self.noise_skipped})")
+
+
+def _accumulators(accum, other):
+    """(a, b or None, pointer to b or None): the statistics' one or two accumulators, neither empty."""
+    a = image(accum, empty=False)
+    if other is None:
+        return a, None, None
+    b = image(other, "second accumulator", empty=False)
+    if b.shape != a.shape:
+        raise ValueError(f"accumulators of shapes {a.shape} and {b.shape}")
+    return a, b, N.fptr(b)
+
+
+def frame_statistics_host(accum: np.ndarray, other: "np.ndarray | None" = None) -> FrameStatistics:
+    """The frame statistics on the CPU (ptsFrameStatistics, libptscene.so):
+    for saved accumulators on a machine without a GPU, and the implementation
+    SampleBuffer.statistics equals bit for bit.  accum, other: (H, W, 4) XYZ
+    sums + sample count; with `other`, an independent render of the same
+    frame, the luminance part describes accum + other and the noise part the
+    pair."""
+    a, b, bp = _accumulators(accum, other)
+    out = N.pt_frame_statistics()
+    pts("ptsFrameStatistics", a.shape[1], a.shape[0], N.fptr(a), bp, C.byref(out))
+    return FrameStatistics(out)
+
+
+def tile_statistics_host(accum: np.ndarray, other: "np.ndarray | None" = None, threshold: float = 0.1) -> np.ndarray:
+    """Per-tile statistics on the CPU (ptsTileStatistics, libptscene.so), which
+    SampleBuffer.tile_statistics equals bit for bit: a (tiles_y, tiles_x) array
+    of TILE_STATS_DTYPE records, one per 16 x 16 tile (clipped at the right and
+    bottom edges).  accum, other: (H, W, 4) accumulators as for
+    frame_statistics_host; without `other`, pair and over are 0.  over counts
+    the pair pixels whose relative half-difference exceeds `threshold`."""
+    a, b, bp = _accumulators(accum, other)
+    out = np.zeros(tile_grid(a.shape[1], a.shape[0]), dtype=N.TILE_STATS_DTYPE)
+    pts("ptsTileStatistics", a.shape[1], a.shape[0], N.fptr(a), bp, float(threshold), out.ctypes.data)
+    return out
+
+
+def tile_mask_of_region(width: int, height: int, x0: int, y0: int, x1: int, y1: int) -> np.ndarray:
+    """The (tiles_y, tiles_x) uint8 mask of the 16 x 16 tiles of a width x
+    height frame that hold a pixel of [x0, x1) x [y0, y1) (clipped to the
+    frame): the argument of BasicRenderer.set_active_tiles that re-renders
+    that region."""
+    ty, tx = tile_grid(width, height)
+    mask = np.zeros((ty, tx), dtype=np.uint8)
+    x0, y0, x1, y1 = max(int(x0), 0), max(int(y0), 0), min(int(x1), int(width)), min(int(y1), int(height))
+    if x0 < x1 and y0 < y1:
+        mask[y0 // N.TILE_SIZE:(y1 - 1) // N.TILE_SIZE + 1, x0 // N.TILE_SIZE:(x1 - 1) // N.TILE_SIZE + 1] = 1
+    return mask
+
+
+def denoise_host(accum: np.ndarray, guides: np.ndarray, params: "DenoiseParameters | None" = None) -> np.ndarray:
+    """The denoiser on the CPU (ptsDenoise, libptscene.so): for saved
+    accumulators on a machine without a GPU, and the implementation the
+    device filter equals bit for bit.  accum: (H, W, 4) XYZ sums + sample
+    count; guides: (H, W) DENOISE_GUIDE_DTYPE records.  Returns (H, W, 4):
+    the denoised mean XYZ and 1 (zeros where the count is not positive)."""
+    a = image(accum)
+    g = guide_image(guides, a)
+    out = np.zeros_like(a)
+    p = (params or DenoiseParameters()).as_struct()
+    pts("ptsDenoise", a.shape[1], a.shape[0], N.fptr(a), g.ctypes.data, C.byref(p), N.fptr(out))
+    return out
+
+
+def denoise_pair_host(accum_a: np.ndarray, accum_b: np.ndarray, guides: np.ndarray,
+                      params: "DenoisePairParameters | None" = None) -> np.ndarray:
+    """The variance-guided denoiser on the CPU (ptsDenoisePair,
+    libptscene.so), which the device filter equals bit for bit.  accum_a,
+    accum_b: (H, W, 4) accumulators of two independent renders of one frame
+    (FrameIndex apart by 1 << 24); guides: (H, W) DENOISE_GUIDE_DTYPE records.
+    Returns (H, W, 4): the denoised mean XYZ of a + b and 1 (zeros where the
+    combined count is not positive)."""
+    a, b = (np.ascontiguousarray(x, dtype=np.float32) for x in (accum_a, accum_b))   # both, before either is judged
+    a = image(a)
+    b = image_like(b, a, "second accumulator", "first")
+    g = guide_image(guides, a)
+    out = np.zeros_like(a)
+    p = (params or DenoisePairParameters()).as_struct()
+    pts("ptsDenoisePair", a.shape[1], a.shape[0], N.fptr(a), N.fptr(b), g.ctypes.data, C.byref(p), N.fptr(out))
+    return out
+
+
+def shape_motion(prev_shapes: np.ndarray, shapes: np.ndarray) -> np.ndarray:
+    """The motion table between two packs of one scene (ptsShapeMotion,
+    pt_scene.h): prev_shapes and shapes are the packed
+    shape records (scene.arrays()["shapes"], DeviceScene.shapes) of the
+    previous and the current frame; returns one SHAPE_MOTION_DTYPE record per
+    current shape.  Shapes are matched by index: the set of entities must be
+    the same in both packs (only a longer array is noticed)."""
+    ps = np.ascontiguousarray(prev_shapes, dtype=N.SHAPE_DTYPE).reshape(-1)
+    cs = np.ascontiguousarray(shapes, dtype=N.SHAPE_DTYPE).reshape(-1)
+    out = np.zeros(cs.size, dtype=N.SHAPE_MOTION_DTYPE)
+    pts("ptsShapeMotion", ps.ctypes.data if ps.size else None, ps.size, cs.ctypes.data if cs.size else None, cs.size,
+        out.ctypes.data if cs.size else None)
+    return out
+
+
+def reproject_host(prev_accum: np.ndarray, prev_guides: np.ndarray, prev_camera, guides: np.ndarray, camera,
+                   params: "ReprojectParameters | None" = None, motion: "np.ndarray | None" = None) -> np.ndarray:
+    """Temporal reprojection on the CPU (ptsReproject, libptscene.so), which
+    the device kernel equals bit for bit.  prev_accum: (Hp, Wp, 4) accumulator
+    of the previous view; prev_guides: its (Hp, Wp) DENOISE_GUIDE_DTYPE
+    records; guides: the current view's (H, W) records; prev_camera, camera:
+    the packed camera records (scene.arrays()["cameras"][i]) the two guide
+    images were rendered with.  Returns (H, W, 4): (mean XYZ * n, n) with n
+    the carried sample count, zeros where the pixel has no history.  motion:
+    a shape_motion() table; pixels of moved shapes then follow them
+    (ptsReprojectMoving)."""
+    a = image(prev_accum)
+    pg = guide_image(prev_guides, a, "previous guides")
+    g = np.ascontiguousarray(guides, dtype=N.DENOISE_GUIDE_DTYPE)
+    if g.ndim != 2:
+        raise ValueError(f"guides of shape {g.shape}, expected (H, W)")
+    out = np.zeros(g.shape + (4,), np.float32)
+    pc, c = camera_struct(prev_camera), camera_struct(camera)
+    p = (params or ReprojectParameters()).as_struct()
+    views = (a.shape[1], a.shape[0], N.fptr(a), pg.ctypes.data, C.byref(pc), g.shape[1], g.shape[0], g.ctypes.data,
+             C.byref(c))
+    if motion is not None:
+        m, mp, mn = motion_table(motion)
+        pts("ptsReprojectMoving", *views, mp, mn, C.byref(p), N.fptr(out))
+    else:
+        pts("ptsReproject", *views, C.byref(p), N.fptr(out))
+    return out
+
+
+def rectify_host(history: np.ndarray, current: np.ndarray, guides: np.ndarray,
+                 params: "RectifyParameters | None" = None) -> np.ndarray:
+    """History validation on the CPU (ptsRectifyHistory, libptscene.so), which
+    the device kernel equals bit for bit.  history: (H, W, 4) accumulator in
+    (mean * n, n) form, e.g. reproject_host's result; current: the (H, W, 4)
+    accumulator of the new rounds alone; guides: the current view's (H, W)
+    DENOISE_GUIDE_DTYPE records.  Returns the (H, W, 4) history with every
+    pixel's mean pulled into the box its window of current samples allows and
+    the count of a pulled pixel cut."""
+    a = image(history, "history")
+    b = image_like(current, a, "current accumulator", "history")
+    g = guide_image(guides, a)
+    out = np.zeros_like(a)
+    p = (params or RectifyParameters()).as_struct()
+    pts("ptsRectifyHistory", a.shape[1], a.shape[0], N.fptr(a), N.fptr(b), g.ctypes.data, C.byref(p), N.fptr(out))
+    return out
+
+
+def despike_host(accum: np.ndarray, guides: np.ndarray, params: "DespikeParameters | None" = None) -> np.ndarray:
+    """The firefly clamp on the CPU (ptsDespike, libptscene.so), which the
+    device kernel equals bit for bit.  accum: (H, W, 4) XYZ sums + sample
+    count; guides: the same view's (H, W) DENOISE_GUIDE_DTYPE records.
+    Returns the (H, W, 4) accumulator with the colour sums of every pixel that
+    stands out of its window scaled down onto the window's limit; every other
+    pixel and every count keeps its bits."""
+    a = image(accum)
+    g = guide_image(guides, a)
+    out = np.zeros_like(a)
+    p = (params or DespikeParameters()).as_struct()
+    pts("ptsDespike", a.shape[1], a.shape[0], N.fptr(a), g.ctypes.data, C.byref(p), N.fptr(out))
+    return out
