@@ -281,7 +281,8 @@ int                ptSetBasicRendererRoundBatch(pt_basic_renderer* renderer, uin
  * every hardware queue of the process and measured slower).
  * ptGetBasicRendererSplit reports the K that consecutive rounds use now, the
  * tiles of group 0 (the launches kernel profiling times) and all tiles; any
- * pointer may be NULL.  Default 0. */
+ * pointer may be NULL.  Default 0.  Under the RUN block map (below) a group
+ * owns whole runs of four tiles: runs u % K instead of tiles t % K. */
 #define PT_MAX_SPLIT 4
 /* Class-pure shade inside tile groups (no reference counterpart: a launch
  * schedule).  In scenes with more than one material type, the rounds of a
@@ -321,6 +322,34 @@ int                ptReadBasicRendererRayPositions(pt_device* device, pt_basic_r
 int                ptSetBasicRendererSplit(pt_basic_renderer* renderer, uint32_t groups);
 int                ptGetBasicRendererSplit(const pt_basic_renderer* renderer, uint32_t* groups, uint32_t* timed_tiles,
                                            uint32_t* tiles);
+/* Block map (no reference counterpart: which extend block traces which ray
+ * positions; results are identical under every map; include/pt_blockmap.h,
+ * DESIGN.md §4 "Block map").  TILE: a block traces one tile's four quarters of
+ * 64 positions.  RUN: a block traces one quarter of each of four consecutive
+ * tiles, so that under LENGTH order its four waves have one predicted length;
+ * tile groups then own whole runs of four tiles and extend is dispatched by an
+ * order over (run, quarter) units.  RUN runs where LENGTH order does, in
+ * rounds issued as separate launches (not fused rounds or round batches) with
+ * no active tile set in place; a renderer set to RUN where it never can (a
+ * scene LENGTH order does not run on) refuses its rounds with a message.
+ * AUTO (default) = RUN wherever it runs.  ptGetBasicRendererBlockMap: the map
+ * set and the map the next rounds use (either pointer may be NULL).
+ * ptBlockMap*: the host's view of include/pt_blockmap.h for granule 1 (TILE)
+ * or 4 (RUN) -- a group's tiles and units, where its segments of the two
+ * orders start, and the tile and quarter wave 0..3 of a unit's block traces
+ * (the tile may lie past the last one: the wave then traces nothing).  They
+ * return 0 for a granule other than 1 or 4 or groups == 0. */
+enum { PT_BLOCK_MAP_AUTO = 0, PT_BLOCK_MAP_TILE = 1, PT_BLOCK_MAP_RUN = 2 };
+int                ptSetBasicRendererBlockMap(pt_basic_renderer* renderer, uint32_t map);
+int                ptGetBasicRendererBlockMap(const pt_basic_renderer* renderer, uint32_t* map, uint32_t* used);
+uint32_t           ptBlockMapGroupTileCount(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule);
+uint32_t           ptBlockMapGroupTile(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule, uint32_t i);
+uint32_t           ptBlockMapGroupTileStart(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule);
+uint32_t           ptBlockMapGroupUnitCount(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule);
+uint32_t           ptBlockMapGroupUnit(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule, uint32_t i);
+uint32_t           ptBlockMapGroupUnitStart(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule);
+uint32_t           ptBlockMapUnitTile(uint32_t unit, uint32_t wave, uint32_t granule);
+uint32_t           ptBlockMapUnitQuarter(uint32_t unit, uint32_t wave, uint32_t granule);
 /* Active tile set (no reference counterpart): the rounds
  * that follow run on the chosen 16 x 16 tiles only.  A full-frame renderer
  * numbers its tiles row-major: tile (tx, ty) covers the pixels [16 tx, 16 tx +
@@ -432,6 +461,8 @@ typedef struct pt_shade_info {
     uint32_t ray_order;         /* PT_RAY_ORDER_OCTANT or PT_RAY_ORDER_LENGTH: the order the next
                                    unfused rounds place new rays in (AUTO resolved, fall-backs applied) */
     uint32_t length_trained;    /* 1: the scene's length table holds trained classes */
+    uint32_t block_map;         /* PT_BLOCK_MAP_TILE or PT_BLOCK_MAP_RUN: the map the next rounds' extend
+                                   launches use (AUTO resolved, fall-backs applied) */
 } pt_shade_info;
 int                ptGetBasicRendererShadeInfo(pt_basic_renderer* renderer, pt_shade_info* info);
 

@@ -42,10 +42,12 @@ class pt_scene_packs(C.Structure):
 class pt_shade_info(C.Structure):
     """pt_shade_info (include/pt_api.h): the shade variant a renderer runs."""
     _fields_ = [("scene_mask", C.c_uint32), ("kernel_mask", C.c_uint32), ("completion_queue", C.c_uint32),
-                ("grey_records", C.c_uint32), ("ray_order", C.c_uint32), ("length_trained", C.c_uint32)]
+                ("grey_records", C.c_uint32), ("ray_order", C.c_uint32), ("length_trained", C.c_uint32),
+                ("block_map", C.c_uint32)]
 
 
 RAY_ORDER_AUTO, RAY_ORDER_OCTANT, RAY_ORDER_LENGTH = 0, 1, 2   # PT_RAY_ORDER_*
+BLOCK_MAP_AUTO, BLOCK_MAP_TILE, BLOCK_MAP_RUN = 0, 1, 2        # PT_BLOCK_MAP_*
 RAYKEY_COUNT = 32768                                            # PT_RAYKEY_COUNT (include/pt_raykey.h)
 
 
@@ -419,6 +421,16 @@ HIP_API = {
     "ptGetBasicRendererSplit": (_i32, [_vp, _u32ptr, _u32ptr, _u32ptr]),
     "ptSetBasicRendererRayOrder": (_i32, [_vp, _u32]),
     "ptGetBasicRendererRayOrder": (_i32, [_vp, _u32ptr, _u32ptr]),
+    "ptSetBasicRendererBlockMap": (_i32, [_vp, _u32]),
+    "ptGetBasicRendererBlockMap": (_i32, [_vp, _u32ptr, _u32ptr]),
+    "ptBlockMapGroupTileCount": (_u32, [_u32, _u32, _u32, _u32]),
+    "ptBlockMapGroupTile": (_u32, [_u32, _u32, _u32, _u32, _u32]),
+    "ptBlockMapGroupTileStart": (_u32, [_u32, _u32, _u32, _u32]),
+    "ptBlockMapGroupUnitCount": (_u32, [_u32, _u32, _u32, _u32]),
+    "ptBlockMapGroupUnit": (_u32, [_u32, _u32, _u32, _u32, _u32]),
+    "ptBlockMapGroupUnitStart": (_u32, [_u32, _u32, _u32, _u32]),
+    "ptBlockMapUnitTile": (_u32, [_u32, _u32, _u32]),
+    "ptBlockMapUnitQuarter": (_u32, [_u32, _u32, _u32]),
     "ptReadSceneLengthTable": (_i32, [_vp, _vp, _vp, _u32ptr, C.POINTER(C.c_uint64)]),
     "ptReadBasicRendererRayPositions": (_i32, [_vp, _vp, _vp]),
     "ptSetBasicRendererOpenPBR": (_i32, [_vp, _i32]),

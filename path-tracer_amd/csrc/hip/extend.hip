@@ -13,7 +13,7 @@ namespace ptd {
 // 0.3142-0.3149 -> 0.3036-0.3038 and 0.3313-0.3328 -> 0.3228-0.3243 ms.  The
 // one with the cache takes 56 either way.)
 template <class Src, bool SPILL, int MINW, int CAP, class E = uint32_t, bool NC = false, bool MESH = false,
-          bool TRAIN = false>
+          bool TRAIN = false, bool RUN = false>
 __global__ __launch_bounds__(256, (MESH && !NC) ? 8 : MINW) void extend_kernel(dscene S, Src src, uint32_t n,
                                                                                uint32_t* spill, uint32_t spill_stride)
 {
@@ -26,6 +26,8 @@ __global__ __launch_bounds__(256, (MESH && !NC) ? 8 : MINW) void extend_kernel(d
     // Tile order: the slot renderer dispatches the tiles whose waves took
     // longest in the previous round first (tile_order_kernel), so the
     // kernel's tail holds short blocks; each wave records its own time.
+    // RUN: the order lists block-map units (ExtendTile), keyed by their own
+    // waves' times.
     uint32_t tile = blockIdx.x;
     bool timed = false;
     if constexpr (kRendererSource<Src>) {
@@ -34,7 +36,7 @@ __global__ __launch_bounds__(256, (MESH && !NC) ? 8 : MINW) void extend_kernel(d
             timed = true;
         }
     }
-    ExtendTile<Src, SPILL, CAP, E, MESH, TRAIN>(S, src, n, spill, spill_stride, smem, tile, timed, ncache, ncn);
+    ExtendTile<Src, SPILL, CAP, E, MESH, TRAIN, RUN>(S, src, n, spill, spill_stride, smem, tile, timed, ncache, ncn);
 }
 
 // The length table's finalize (LENGTH order), one block after a call's
@@ -169,39 +171,48 @@ uint32_t pt_extend_stack_cap() { return PT_EXTEND_CAP; }
 // stay on the general LaneStep.
 template <class Src>
 static hipError_t LaunchExtend(const ptd::dscene& S, const Src& src, uint32_t n, uint32_t blocks, uint32_t* spill,
-                               bool train, hipStream_t st)
+                               bool train, bool run, hipStream_t st)
 {
     constexpr bool renderer = ptd::kRendererSource<Src>;
     if (train && !ptv::HasTrain(renderer, S.single_mesh != 0, spill != nullptr)) return hipErrorNotSupported;
+    if (run && !ptv::HasRunMap(renderer, S.single_mesh != 0, spill != nullptr)) return hipErrorNotSupported;
     if (n == 0 || blocks == 0) return hipSuccess;
     ptv::SelectStackEntry(S.stack16 != 0, [&](auto entry) {
         using E = typename decltype(entry)::type;
         const bool cache = S.node_cache && ptv::HasNodeCache<E>(spill != nullptr);
         ptv::SelectFlags(
-            [&](auto SPILL, auto NC, auto MESH, auto TRAIN) {
-                if constexpr ((!NC || ptv::HasNodeCache<E>(SPILL)) && (!TRAIN || ptv::HasTrain(renderer, MESH, SPILL)))
-                    hipLaunchKernelGGL((ptd::extend_kernel<Src, SPILL, PT_EXTEND_MINW, PT_EXTEND_CAP, E, NC, MESH, TRAIN>),
-                                       dim3(blocks), dim3(256), 0, st, S, src, n, spill, n);
+            [&](auto SPILL, auto NC, auto MESH, auto TRAIN, auto RUN) {
+                if constexpr ((!NC || ptv::HasNodeCache<E>(SPILL)) && (!TRAIN || ptv::HasTrain(renderer, MESH, SPILL)) &&
+                              (!RUN || ptv::HasRunMap(renderer, MESH, SPILL)))
+                    hipLaunchKernelGGL(
+                        (ptd::extend_kernel<Src, SPILL, PT_EXTEND_MINW, PT_EXTEND_CAP, E, NC, MESH, TRAIN, RUN>),
+                        dim3(blocks), dim3(256), 0, st, S, src, n, spill, n);
             },
-            spill != nullptr, cache, S.single_mesh != 0, train);
+            spill != nullptr, cache, S.single_mesh != 0, train, run);
     });
     return hipGetLastError();
 }
 
 bool pt_length_train_supported(const ptd::dscene& S, bool spill) { return ptv::HasTrain(true, S.single_mesh != 0, spill); }
 
+bool pt_block_map_run_supported(const ptd::dscene& S, bool spill) { return ptv::HasRunMap(true, S.single_mesh != 0, spill); }
+
 hipError_t pt_launch_extend(const ptd::dscene& S, const ptd::dslots& L, const ptd::dframe& F, uint32_t* spill,
-                            hipStream_t st, bool train)
+                            hipStream_t st, bool train, const uint32_t* units, uint32_t unit_count)
 {
     if (train && (!L.len_sum || !L.len_cnt || !L.len_cam)) return hipErrorNotSupported;
-    return LaunchExtend(S, ptd::ray_source_slots{L, F}, L.n, L.tile_count, spill, train, st);
+    if (!units) return LaunchExtend(S, ptd::ray_source_slots{L, F}, L.n, L.tile_count, spill, train, false, st);
+    // RUN: the kernel's order is the unit order, one block per unit.
+    ptd::dslots U = L;
+    U.order = const_cast<uint32_t*>(units);
+    return LaunchExtend(S, ptd::ray_source_slots{U, F}, L.n, unit_count, spill, train, true, st);
 }
 
 hipError_t pt_launch_trace_rays(const ptd::dscene& S, uint32_t n, const float* origins, const uint32_t* vel,
                                 const float* dur, float4* hit, float2* hc, float4* rec, float2* uv, uint32_t* spill,
                                 hipStream_t st)
 {
-    hipError_t e = LaunchExtend(S, ptd::ray_source_arrays{origins, vel, dur, hit, hc}, n, Blocks(n), spill, false, st);
+    hipError_t e = LaunchExtend(S, ptd::ray_source_arrays{origins, vel, dur, hit, hc}, n, Blocks(n), spill, false, false, st);
     if (e != hipSuccess) return e;
     return pt_launch_finalize(S, n, hit, hc, rec, uv, st);
 }

@@ -151,13 +151,25 @@ PT_DEV void ExtendRay(const dscene& S, const Src& src, tstack<SPILL, CAP, E>& st
     src.outcome(slot, cls, S.mat_classes != 0);
 }
 
-// One tile of extend: thread i traces the ray at position tile*256 + i.
-template <class Src, bool SPILL, int CAP, class E, bool MESH = false, bool TRAIN = false>
+// One block of extend.  Thread i traces the ray at position tile*256 + i; RUN
+// (the renderer's RUN block map, include/pt_blockmap.h): `tile` is a unit, and
+// wave w traces the unit's quarter of the w-th tile of its run -- or nothing,
+// in a short run.  The outcome words, the wave's time, the camera count and
+// the stack column all follow the position or the thread as before.
+template <class Src, bool SPILL, int CAP, class E, bool MESH = false, bool TRAIN = false, bool RUN = false>
 PT_DEV void ExtendTile(const dscene& S, const Src& src, uint32_t n, uint32_t* spill, uint32_t spill_stride, E* smem,
                        uint32_t tile, bool timed, const float4* nc = nullptr, uint32_t ncn = 0)
 {
+    static_assert(!RUN || (MESH && !SPILL && kRendererSource<Src>), "the RUN block map rides the renderer's mesh-only loop");
     uint64_t t0 = timed ? __builtin_amdgcn_s_memtime() : 0;
     uint32_t slot = tile * 256 + threadIdx.x;
+    uint32_t first = 0;   // RUN: the wave's first position, in a scalar register
+    if constexpr (RUN) {
+        const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        first = pt_unit_tile(tile, wave, PT_BLOCK_MAP_RUN_GRANULE) * 256 +
+                pt_unit_quarter(tile, wave, PT_BLOCK_MAP_RUN_GRANULE) * 64;
+        slot = first + (threadIdx.x & 63u);
+    }
     if (slot >= n) return;
     tstack<SPILL, CAP, E> st;
     st.lds = &smem[threadIdx.x];
@@ -168,7 +180,7 @@ PT_DEV void ExtendTile(const dscene& S, const Src& src, uint32_t n, uint32_t* sp
     ExtendRay<SPILL, CAP, E, MESH, TRAIN>(S, src, st, slot);
     if constexpr (kRendererSource<Src>) {
         if (timed && (threadIdx.x & 63u) == 0)
-            src.L.tilecost[tile * 4 + (threadIdx.x >> 6)] = (uint32_t)(__builtin_amdgcn_s_memtime() - t0);
+            src.L.tilecost[RUN ? first >> 6 : tile * 4 + (threadIdx.x >> 6)] = (uint32_t)(__builtin_amdgcn_s_memtime() - t0);
     }
 }
 

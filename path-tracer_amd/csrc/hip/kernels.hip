@@ -8,35 +8,28 @@
 
 namespace ptd {
 
-// Longest-first dispatch order for the next extend: tiles by their slowest
-// wave's time, descending, by a one-block counting sort over 512 log-spaced
-// buckets (16 per octave).  Any order gives the same results; only the
-// kernel's tail changes.
-//
-// Tile groups (ptSetBasicRendererSplit): group g of K owns the tiles
-// t = g, g + K, ... and its segment order[start, start + count) of the
-// dispatch order, which it sorts on its own stream; K = 1 is the whole frame.
-__global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* cost, uint32_t* order, uint32_t tiles,
-                                                          uint32_t groups, uint32_t group, uint32_t start)
+// One longest-first counting sort by the whole block: item(i), i < n, names
+// the i-th thing to order and time(x) gives its time; out[0, n) receives the
+// items over 512 log-spaced buckets (16 per octave), longest first.
+template <class Item, class Time>
+PT_DEV void SortLongestFirst(uint32_t n, uint32_t* out, uint32_t* count, uint32_t* wsum, Item item, Time time)
 {
-    const uint32_t nt = pt_tile_group_count(tiles, groups, group);
-    __shared__ uint32_t count[512];
+    __syncthreads();   // a sort before this one is done with count[]
     for (uint32_t i = threadIdx.x; i < 512; i += 1024) count[i] = 0;
     __syncthreads();
-    auto key = [&](uint32_t t) -> uint32_t {
-        uint32_t c = max(max(cost[4 * t], cost[4 * t + 1]), max(cost[4 * t + 2], cost[4 * t + 3]));
+    auto key = [&](uint32_t x) -> uint32_t {
+        uint32_t c = time(x);
         if (c < 16) return 511u;                               // untimed / trivial: last
         uint32_t e = 31u - __clz(c);                           // octave
         uint32_t m = (c >> (e - 4)) & 15u;                     // 16 steps inside it
         uint32_t k = min(e * 16u + m, 511u);
         return 511u - k;                                       // longest first
     };
-    for (uint32_t i = threadIdx.x; i < nt; i += 1024) atomicAdd(&count[key(pt_tile_group_tile(tiles, groups, group, i))], 1u);
+    for (uint32_t i = threadIdx.x; i < n; i += 1024) atomicAdd(&count[key(item(i))], 1u);
     __syncthreads();
     // Exclusive scan of the 512 buckets: eight waves scan 64 each with
     // shuffles, then add the totals of the waves before them (a serial scan
     // by one thread was most of this kernel's 11 us).
-    __shared__ uint32_t wsum[8];
     uint32_t c = 0, incl = 0;
     if (threadIdx.x < 512) {
         c = count[threadIdx.x];
@@ -54,9 +47,56 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* cost, 
         count[threadIdx.x] = before + incl - c;
     }
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < nt; i += 1024) {
-        const uint32_t t = pt_tile_group_tile(tiles, groups, group, i);
-        order[start + atomicAdd(&count[key(t)], 1u)] = t;
+    for (uint32_t i = threadIdx.x; i < n; i += 1024) {
+        const uint32_t x = item(i);
+        out[atomicAdd(&count[key(x)], 1u)] = x;
+    }
+}
+
+// Longest-first dispatch order for the next round: tiles by their slowest
+// wave's time, descending.  Any order gives the same results; only the
+// kernels' tails change.
+//
+// Tile groups (ptSetBasicRendererSplit; include/pt_blockmap.h): group g of K
+// owns the tiles t = g, g + K, ... and its segment order[start, start + count)
+// of the dispatch order, which it sorts on its own stream; K = 1 is the whole
+// frame.
+//
+// UNITS (the RUN block map): the group owns whole runs of four tiles, and a
+// second block of the same launch sorts its segment of the unit order, which
+// extend then dispatches by: unit (run u, quarter j) by the longest of the
+// quarter-j waves of the run's tiles, each timed by the block that traced it.
+// Shade keeps the tile order.
+template <bool UNITS>
+__global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* cost, uint32_t* order, uint32_t tiles,
+                                                          uint32_t groups, uint32_t group, uint32_t start,
+                                                          uint32_t* units, uint32_t ustart)
+{
+    __shared__ uint32_t count[512];
+    __shared__ uint32_t wsum[8];
+    auto tile_time = [&](uint32_t t) {
+        return max(max(cost[4 * t], cost[4 * t + 1]), max(cost[4 * t + 2], cost[4 * t + 3]));
+    };
+    if constexpr (!UNITS) {
+        SortLongestFirst(pt_tile_group_count(tiles, groups, group), order + start, count, wsum,
+                         [&](uint32_t i) { return pt_tile_group_tile(tiles, groups, group, i); }, tile_time);
+    } else {
+        // Two blocks, one order each, so that the launch takes one sort's time.
+        constexpr uint32_t G = PT_BLOCK_MAP_RUN_GRANULE;
+        if (blockIdx.x == 0)
+            SortLongestFirst(pt_group_tile_count(tiles, groups, group, G), order + start, count, wsum,
+                             [&](uint32_t i) { return pt_group_tile(groups, group, i, G); }, tile_time);
+        else
+            SortLongestFirst(pt_group_unit_count(tiles, groups, group, G), units + ustart, count, wsum,
+                             [&](uint32_t i) { return pt_group_unit(groups, group, i, G); },
+                             [&](uint32_t x) {
+                                 uint32_t c = 0;
+                                 for (uint32_t w = 0; w < 4; w++) {
+                                     const uint32_t t = pt_unit_tile(x, w, G);
+                                     if (t < tiles) c = max(c, cost[4 * t + pt_unit_quarter(x, w, G)]);
+                                 }
+                                 return c;
+                             });
     }
 }
 
@@ -201,11 +241,19 @@ hipError_t pt_launch_guard(const uint32_t* done, uint32_t words, uint64_t target
     return hipGetLastError();
 }
 
-hipError_t pt_launch_tile_order(const ptd::dslots& L, hipStream_t st, uint32_t groups, uint32_t group)
+hipError_t pt_launch_tile_order(const ptd::dslots& L, hipStream_t st, uint32_t groups, uint32_t group, uint32_t granule,
+                                uint32_t* units)
 {
     if (!L.order || L.tile_count == 0 || groups == 0 || group >= groups) return hipSuccess;
-    hipLaunchKernelGGL(ptd::tile_order_kernel, dim3(1), dim3(1024), 0, st, L.tilecost, L.order, L.tile_count, groups,
-                       group, pt_tile_group_start(L.tile_count, groups, group));
+    if (granule == PT_BLOCK_MAP_RUN_GRANULE) {
+        if (!units) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(ptd::tile_order_kernel<true>, dim3(2), dim3(1024), 0, st, L.tilecost, L.order, L.tile_count,
+                           groups, group, pt_group_tile_start(L.tile_count, groups, group, granule), units,
+                           pt_group_unit_start(L.tile_count, groups, group, granule));
+    } else {
+        hipLaunchKernelGGL(ptd::tile_order_kernel<false>, dim3(1), dim3(1024), 0, st, L.tilecost, L.order, L.tile_count,
+                           groups, group, pt_tile_group_start(L.tile_count, groups, group), (uint32_t*)nullptr, 0u);
+    }
     return hipGetLastError();
 }
 

@@ -7,6 +7,7 @@
 #include "../../../include/pt_packed.h"
 #include "../../../include/pt_api.h"
 #include "../../../include/pt_raykey.h"
+#include "../../../include/pt_blockmap.h"
 
 namespace ptd {
 
@@ -81,8 +82,13 @@ hipError_t pt_launch_raygen(const ptd::dscene& S, const ptd::dslots& L, const pt
                             hipStream_t st);
 // train: the training instantiation (LENGTH order; L.len_sum, len_cnt and
 // len_cam set), which pt_length_train_supported has for the scene.
+// units: the RUN block map (include/pt_blockmap.h) -- one block per entry of
+// this segment of the unit order, `unit_count` of them, instead of one per
+// tile of L.order; for the scenes pt_block_map_run_supported accepts.
 hipError_t pt_launch_extend(const ptd::dscene& S, const ptd::dslots& L, const ptd::dframe& F, uint32_t* spill,
-                            hipStream_t st, bool train = false);
+                            hipStream_t st, bool train = false, const uint32_t* units = nullptr,
+                            uint32_t unit_count = 0);
+bool pt_block_map_run_supported(const ptd::dscene& S, bool spill);
 // Ray order LENGTH: the scenes whose extend has a training instantiation (the
 // mesh-only loop without a spilled stack) and the shade masks whose tile shade
 // has a LENGTH instantiation (pt_launch_shade takes it when L.len_order is
@@ -221,10 +227,11 @@ hipError_t pt_launch_shade_classq(const ptd::dscene& S, const ptd::dslots& L, co
                                   uint32_t* next_counts, uint32_t* list, hipStream_t st, uint32_t tiles_all = 0,
                                   uint32_t groups = 1, uint32_t group = 0);
 hipError_t pt_launch_vertex_decode(const uint2* v, uint32_t n, float4* attr, float* vv, hipStream_t st);
-// Tile groups (ptSetBasicRendererSplit): group g of K owns tiles g, g + K, ...
-// (pt_tile_group_count of them) and the dispatch-order segment starting at
-// pt_tile_group_start.  pt_launch_tile_order sorts one group's segment
-// longest-first (groups = 1: the whole frame).
+// Tile groups (ptSetBasicRendererSplit; include/pt_blockmap.h): group g of K
+// owns the granules g, g + K, ... -- tiles (granule 1), or runs of four tiles
+// under the RUN block map (granule 4) -- and its segment of the dispatch
+// orders.  The three below are the granule-1 forms (t % K == g), which the
+// class-list shade derives a group's tiles from.
 __host__ __device__ inline uint32_t pt_tile_group_count(uint32_t tiles, uint32_t groups, uint32_t group)
 {
     return group < tiles ? (tiles - group + groups - 1) / groups : 0u;
@@ -240,7 +247,12 @@ __host__ __device__ inline uint32_t pt_tile_group_start(uint32_t tiles, uint32_t
     for (uint32_t h = 0; h < group; h++) s += pt_tile_group_count(tiles, groups, h);
     return s;
 }
-hipError_t pt_launch_tile_order(const ptd::dslots& L, hipStream_t st, uint32_t groups = 1, uint32_t group = 0);
+// Sorts one group's segment of the tile order L.order longest-first (groups =
+// 1: the whole frame) and, for granule 4, the group's segment of the unit
+// order `units` in the same launch (a block each): unit (run u, quarter j) keyed by the
+// longest quarter-j wave of the run's tiles.
+hipError_t pt_launch_tile_order(const ptd::dslots& L, hipStream_t st, uint32_t groups = 1, uint32_t group = 0,
+                                uint32_t granule = 1, uint32_t* units = nullptr);
 // Guarded rounds (ptRenderFrame): flags[0] := 1 once the done words' sum (the
 // paths completed since the Reset, ptGetStats) reaches target; while it is
 // 0, flags[1] counts the rounds that run.

@@ -44,6 +44,7 @@ pt_basic_renderer* ptCreateBasicRendererStreams(pt_device* d, pt_scene* s, pt_sa
               r->act.alloc_zero(ns) == hipSuccess && r->pos.alloc(ns) == hipSuccess && r->slotof.alloc(ns) == hipSuccess &&
               r->outcome.alloc_zero(tiles * 4 * ptd::PT_OUTCOME_CLASSES + 1) == hipSuccess &&
               r->tilecost.alloc_zero(tiles * 4 + 1) == hipSuccess && r->order.alloc(tiles + 1) == hipSuccess &&
+              r->units.alloc(pt_unit_count((uint32_t)tiles, PT_BLOCK_MAP_RUN_GRANULE) + 1) == hipSuccess &&
               r->done.alloc_zero(ns / 64 + 1) == hipSuccess &&
               (streams == 1 || r->accx.alloc_zero((size_t)streams * frame_px) == hipSuccess);
     if (ok && ns) {
@@ -188,6 +189,73 @@ int ptGetBasicRendererRayOrder(const pt_basic_renderer* r, uint32_t* order, uint
     return 0;
 }
 
+int ptSetBasicRendererBlockMap(pt_basic_renderer* r, uint32_t map)
+{
+    if (!r || map > PT_BLOCK_MAP_RUN) {
+        SetError("ptSetBasicRendererBlockMap: bad argument (0 automatic, 1 tile, 2 run)");
+        return -1;
+    }
+    if (map == PT_BLOCK_MAP_RUN && r->scene && r->scene->valid && !RunMapPossible(r)) {
+        SetError("ptSetBasicRendererBlockMap: the RUN block map runs where ray order LENGTH does "
+                 "(a one-mesh diffuse scene without a spilled stack, ray order not OCTANT)");
+        return -1;
+    }
+    r->block_map = map;
+    return 0;
+}
+
+int ptGetBasicRendererBlockMap(const pt_basic_renderer* r, uint32_t* map, uint32_t* used)
+{
+    if (!r) { SetError("ptGetBasicRendererBlockMap: null renderer"); return -1; }
+    if (used && (!r->scene || !r->scene->valid)) {
+        SetError("renderer: scene has no valid packs (call ptUpdateScene)");
+        return -1;
+    }
+    if (map) *map = r->block_map;
+    if (used) *used = RunMap(r) ? PT_BLOCK_MAP_RUN : PT_BLOCK_MAP_TILE;
+    return 0;
+}
+
+// The host's view of include/pt_blockmap.h (tests, tools).
+static bool MapArgs(uint32_t groups, uint32_t granule)
+{
+    return groups != 0 && (granule == PT_BLOCK_MAP_TILE_GRANULE || granule == PT_BLOCK_MAP_RUN_GRANULE);
+}
+uint32_t ptBlockMapGroupTileCount(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule)
+{
+    return MapArgs(groups, granule) ? pt_group_tile_count(tiles, groups, group, granule) : 0u;
+}
+uint32_t ptBlockMapGroupTile(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule, uint32_t i)
+{
+    return MapArgs(groups, granule) && i < pt_group_tile_count(tiles, groups, group, granule)
+               ? pt_group_tile(groups, group, i, granule) : 0u;
+}
+uint32_t ptBlockMapGroupTileStart(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule)
+{
+    return MapArgs(groups, granule) ? pt_group_tile_start(tiles, groups, std::min(group, groups), granule) : 0u;
+}
+uint32_t ptBlockMapGroupUnitCount(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule)
+{
+    return MapArgs(groups, granule) ? pt_group_unit_count(tiles, groups, group, granule) : 0u;
+}
+uint32_t ptBlockMapGroupUnit(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule, uint32_t i)
+{
+    return MapArgs(groups, granule) && i < pt_group_unit_count(tiles, groups, group, granule)
+               ? pt_group_unit(groups, group, i, granule) : 0u;
+}
+uint32_t ptBlockMapGroupUnitStart(uint32_t tiles, uint32_t groups, uint32_t group, uint32_t granule)
+{
+    return MapArgs(groups, granule) ? pt_group_unit_start(tiles, groups, std::min(group, groups), granule) : 0u;
+}
+uint32_t ptBlockMapUnitTile(uint32_t unit, uint32_t wave, uint32_t granule)
+{
+    return MapArgs(1, granule) && wave < 4 ? pt_unit_tile(unit, wave, granule) : 0u;
+}
+uint32_t ptBlockMapUnitQuarter(uint32_t unit, uint32_t wave, uint32_t granule)
+{
+    return MapArgs(1, granule) && wave < 4 ? pt_unit_quarter(unit, wave, granule) : 0u;
+}
+
 int ptReadBasicRendererRayPositions(pt_device* d, pt_basic_renderer* r, uint16_t* positions)
 {
     if (!d || !r || !positions) { SetError("ptReadBasicRendererRayPositions: null argument"); return -1; }
@@ -212,7 +280,7 @@ int ptGetBasicRendererSplit(const pt_basic_renderer* r, uint32_t* groups, uint32
     if (!r) { SetError("ptGetBasicRendererSplit: null renderer"); return -1; }
     const uint32_t K = SplitGroups(r);
     if (groups) *groups = K;
-    if (timed_tiles) *timed_tiles = pt_tile_group_count(r->slots.tile_count, K, 0);
+    if (timed_tiles) *timed_tiles = pt_group_tile_count(r->slots.tile_count, K, 0, K > 1 ? OrderGranule(r) : 1u);
     if (tiles) *tiles = r->slots.tile_count;
     return 0;
 }
@@ -440,6 +508,7 @@ int ptGetBasicRendererShadeInfo(pt_basic_renderer* r, pt_shade_info* info)
     info->grey_records = r->grey ? 1u : 0u;
     info->ray_order = LengthOrder(r) ? PT_RAY_ORDER_LENGTH : PT_RAY_ORDER_OCTANT;
     info->length_trained = r->scene->len_trained ? 1u : 0u;
+    info->block_map = RunMap(r) ? PT_BLOCK_MAP_RUN : PT_BLOCK_MAP_TILE;
     return 0;
 }
 

@@ -231,6 +231,31 @@ bool ptrt::LengthOrder(const pt_basic_renderer* r)
     return r->ray_order != PT_RAY_ORDER_OCTANT && LengthSupported(r);
 }
 
+// --- block map (ptSetBasicRendererBlockMap; DESIGN.md §4 "Block map") -----------
+// RUN gives each extend block one quarter of four neighbouring tiles, which
+// under LENGTH order are four waves of one predicted length: the block no
+// longer holds three empty wave slots and its LDS while one long wave ends.
+// It runs where LENGTH order does and extend has the instantiation, in rounds
+// issued as separate launches over every tile: fused rounds and round batches
+// trace a tile per block, and an active tile set breaks runs.  Tile groups
+// then own whole runs (OrderGranule), so that a run's tiles stay neighbours.
+bool ptrt::RunMapPossible(const pt_basic_renderer* r)
+{
+    return LengthOrder(r) && pt_block_map_run_supported(r->scene->d, Spills(r));
+}
+
+// AUTO: RUN wherever it runs (C3 +2.2 %, C4 +4.9 %: DESIGN.md §4 "Block map").
+bool ptrt::RunMap(const pt_basic_renderer* r)
+{
+    return r->block_map != PT_BLOCK_MAP_TILE && RunMapPossible(r) && !Masked(r) && r->round_batch < 2 &&
+           !RoundFused(r, ActiveSlots(r));
+}
+
+uint32_t ptrt::OrderGranule(const pt_basic_renderer* r)
+{
+    return RunMap(r) ? PT_BLOCK_MAP_RUN_GRANULE : PT_BLOCK_MAP_TILE_GRANULE;
+}
+
 // The order of the launches that follow, in the renderer's slots (every
 // round's view is cut from them).
 int ptrt::SyncRayOrder(pt_basic_renderer* r)
@@ -281,40 +306,51 @@ static int LengthFinalize(pt_device* d, pt_basic_renderer* r)
     return SyncRayOrder(r);
 }
 
-// Rewrites the dispatch order for K groups, each group's tiles in its own
-// segment in natural order; with an active tile set, a segment's active tiles
-// first (group_active of them), the inactive ones behind.  Waits for the
-// device first: queued launches may still read the array.
-static int WriteOrder(pt_device* d, pt_basic_renderer* r, uint32_t K)
+// Rewrites the dispatch order for K groups of tiles (granule 1) or of runs
+// (granule 4: the RUN block map, never with an active tile set), each group's
+// tiles in its own segment in natural order and, for granule 4, its units in
+// theirs; with an active tile set, a segment's active tiles first
+// (group_active of them), the inactive ones behind.  Waits for the device
+// first: queued launches may still read the arrays.
+static int WriteOrder(pt_device* d, pt_basic_renderer* r, uint32_t K, uint32_t granule)
 {
     if (!r->slots.order) return 0;
     const uint32_t T = r->slots.tile_count;
-    std::vector<uint32_t> order(T);
+    std::vector<uint32_t> order(T), units;
     uint32_t i = 0;
     for (uint32_t g = 0; g < PT_MAX_SPLIT; g++) r->group_active[g] = 0;
     for (uint32_t g = 0; g < K; g++) {
-        const uint32_t n = pt_tile_group_count(T, K, g);
+        const uint32_t n = pt_group_tile_count(T, K, g, granule);
         for (uint32_t pass = 0; pass < (Masked(r) ? 2u : 1u); pass++) {
             for (uint32_t j = 0; j < n; j++) {
-                const uint32_t t = pt_tile_group_tile(T, K, g, j);
+                const uint32_t t = pt_group_tile(K, g, j, granule);
                 if (Masked(r) && (r->mask[t] != 0) != (pass == 0)) continue;
                 order[i++] = t;
                 if (Masked(r) && pass == 0) r->group_active[g]++;
             }
         }
+        if (granule == PT_BLOCK_MAP_RUN_GRANULE)
+            for (uint32_t j = 0; j < pt_group_unit_count(T, K, g, granule); j++)
+                units.push_back(pt_group_unit(K, g, j, granule));
     }
     PT_WAIT(d);
     PT_HIP(hipMemcpy(r->order.ptr, order.data(), (size_t)T * 4, hipMemcpyHostToDevice));
+    if (!units.empty()) PT_HIP(hipMemcpy(r->units.ptr, units.data(), units.size() * 4, hipMemcpyHostToDevice));
     r->order_groups = K;
+    r->order_granule = granule;
     return 0;
 }
 
 // The dispatch order holds each group's tiles in its own segment; a change of
-// K restarts it from the natural order of each group.
-static int EnsureOrderGroups(pt_device* d, pt_basic_renderer* r, uint32_t K)
+// K or of the granule restarts it from the natural order of each group.  A
+// single-stream round over every tile runs on any group structure (its
+// launches cover the whole arrays), but needs the granule of its block map.
+static int EnsureOrderGroups(pt_device* d, pt_basic_renderer* r, uint32_t K, uint32_t granule)
 {
-    if (r->order_groups == K || !r->slots.order) return 0;
-    return WriteOrder(d, r, K);
+    if (!r->slots.order) return 0;
+    const bool grouped = K > 1 || Masked(r);
+    if (r->order_granule == granule && (!grouped || r->order_groups == K)) return 0;
+    return WriteOrder(d, r, grouped ? K : r->order_groups, granule);
 }
 
 static int EnsureGroupStreams(pt_device* d, uint32_t K)
@@ -375,6 +411,7 @@ struct round_setup {
     bool compact;       // ShadeCompact
     bool fused;         // a round is one round_kernel launch (single-stream rounds only)
     bool lists;         // an unfused round shades through class lists
+    bool run;           // an unfused round's extend takes the RUN block map (RunMap)
 };
 
 // Before the rounds of a call that run in K tile groups (1: on the device
@@ -392,10 +429,14 @@ static int BeginRounds(pt_device* d, pt_basic_renderer* r, uint32_t K, uint64_t 
         r->params.FrameIndex += (uint32_t)seeds;
         return 0;
     }
+    if (r->block_map == PT_BLOCK_MAP_RUN && !RunMapPossible(r)) {
+        SetError("renderer: the RUN block map does not run on this scene and ray order (ptSetBasicRendererBlockMap)");
+        return -1;
+    }
     if (int e = EnsureSpill(r)) return e;
     if (int e = SyncRecordForm(d, r)) return e;
-    if (K > 1 || Masked(r))
-        if (int e = EnsureOrderGroups(d, r, K)) return e;
+    S.run = RunMap(r);
+    if (int e = EnsureOrderGroups(d, r, K, OrderGranule(r))) return e;
     if (K > 1)
         if (int e = EnsureGroupStreams(d, K)) return e;
     S.F = Frame(r);
@@ -442,10 +483,12 @@ static void RoundsDone(pt_device* d, pt_basic_renderer* r, uint32_t n, uint32_t 
     if (r->slots.order) r->order_tick += n;
 }
 
-// Longest-first re-sort of the order array's groups g0 .. g1 - 1 on st.
+// Longest-first re-sort of the order array's groups g0 .. g1 - 1 on st (and
+// of their units, when the groups own runs).
 static int Resort(pt_basic_renderer* r, uint32_t g0, uint32_t g1, hipStream_t st)
 {
-    for (uint32_t g = g0; g < g1; g++) PT_HIP(pt_launch_tile_order(r->slots, st, r->order_groups, g));
+    for (uint32_t g = g0; g < g1; g++)
+        PT_HIP(pt_launch_tile_order(r->slots, st, r->order_groups, g, r->order_granule, r->units.ptr));
     return 0;
 }
 
@@ -465,7 +508,16 @@ static int IssueRound(pt_device* d, pt_basic_renderer* r, const round_setup& S, 
         return EndTimed(d, ep);
     }
     if (int e = BeginTimed(d, PT_KERNEL_EXTEND, ep, timed)) return e;
-    PT_HIP(pt_launch_extend(r->scene->d, L, S.F, L.spill, st, train));
+    if (S.run) {
+        // The view's units: group g's segment of the unit order, or all of it.
+        constexpr uint32_t G = PT_BLOCK_MAP_RUN_GRANULE;
+        const uint32_t T = r->slots.tile_count;
+        const uint32_t* units = r->units.ptr + (K > 1 ? pt_group_unit_start(T, K, g, G) : 0u);
+        PT_HIP(pt_launch_extend(r->scene->d, L, S.F, L.spill, st, train, units,
+                                K > 1 ? pt_group_unit_count(T, K, g, G) : pt_unit_count(T, G)));
+    } else {
+        PT_HIP(pt_launch_extend(r->scene->d, L, S.F, L.spill, st, train));
+    }
     if (int e = EndTimed(d, ep)) return e;
     if (int e = BeginTimed(d, PT_KERNEL_SHADE, ep, timed)) return e;
     if (S.lists) {
@@ -515,8 +567,8 @@ static int SplitRounds(pt_device* d, pt_basic_renderer* r, const round_setup& S,
     hipStream_t St[PT_MAX_SPLIT];
     for (uint32_t g = 0; g < K; g++) {
         G[g] = r->slots;
-        G[g].order = r->slots.order + pt_tile_group_start(r->slots.tile_count, K, g);
-        G[g].tile_count = Masked(r) ? r->group_active[g] : pt_tile_group_count(r->slots.tile_count, K, g);
+        G[g].order = r->slots.order + pt_group_tile_start(r->slots.tile_count, K, g, r->order_granule);
+        G[g].tile_count = Masked(r) ? r->group_active[g] : pt_group_tile_count(r->slots.tile_count, K, g, r->order_granule);
         St[g] = g ? d->group_stream[g - 1] : d->stream;
     }
     if (S.lists)
@@ -703,7 +755,9 @@ int ptSetBasicRendererActiveTiles(pt_device* d, pt_basic_renderer* r, const uint
             r->active_slots += (uint64_t)std::min(16u, w - tx * 16u) * std::min(16u, h - ty * 16u);
         }
     }
-    if (int e = WriteOrder(d, r, r->order_groups)) {
+    // Groups of tiles: the RUN block map is off while a set is in place, and
+    // the next unmasked round restores its runs (EnsureOrderGroups).
+    if (int e = WriteOrder(d, r, r->order_groups, PT_BLOCK_MAP_TILE_GRANULE)) {
         // The order array is as it was: so is the set.
         r->mask.swap(previous);
         r->active_tiles = previous_tiles;

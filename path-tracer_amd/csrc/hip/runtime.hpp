@@ -231,6 +231,13 @@ struct pt_basic_renderer {
     uint32_t split = 0;                 // tile groups of consecutive rounds (ptSetBasicRendererSplit): 0 auto, 1 off
     ptrt::dbuf<uint32_t> guard;         // guarded rounds' {stop, rounds run} (ptRenderFrame)
     uint32_t order_groups = 1;          // the group structure the order array holds (tile_order_kernel)
+    // Block map (ptSetBasicRendererBlockMap; include/pt_blockmap.h).  While
+    // the order array's groups own whole runs (order_granule 4), `units`
+    // holds the dispatch order of extend's (run, quarter) units in the same
+    // group segments; under granule 1 it is not kept.
+    uint32_t block_map = PT_BLOCK_MAP_AUTO;
+    uint32_t order_granule = PT_BLOCK_MAP_TILE_GRANULE;
+    ptrt::dbuf<uint32_t> units;
     // Active tile set (ptSetBasicRendererActiveTiles): one byte per tile, empty
     // = every tile.  While set, each group's segment of the order array holds
     // the group's active tiles first, in natural order (WriteOrder), and the
@@ -378,6 +385,9 @@ bool ShadeCompact(const pt_basic_renderer* r);       // the shade kernel's compl
 uint32_t SplitGroups(const pt_basic_renderer* r);    // tile groups of consecutive rounds
 bool ClassListRounds(const pt_basic_renderer* r);    // rounds shade through class lists
 bool LengthOrder(const pt_basic_renderer* r);        // rays are placed by predicted traversal length
+bool RunMapPossible(const pt_basic_renderer* r);     // the RUN block map can run on the renderer's scene and ray order
+bool RunMap(const pt_basic_renderer* r);             // the next rounds' extend launches take the RUN block map
+uint32_t OrderGranule(const pt_basic_renderer* r);   // the granule tile groups own under the map in use (1 or 4)
 int SyncRayOrder(pt_basic_renderer* r);              // sets the slots' ray order for the launches that follow
 
 }  // namespace ptrt

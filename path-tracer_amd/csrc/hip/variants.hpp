@@ -95,4 +95,9 @@ constexpr bool HasNodeCache(bool spill) { return sizeof(E) == 2 && !spill; }
 // renderer's mesh-only loop, unspilled.
 constexpr bool HasTrain(bool renderer_source, bool mesh, bool spill) { return renderer_source && mesh && !spill; }
 
+// The RUN block map's instantiations (ExtendTile's RUN) exist where LENGTH
+// order can run, which gives a run's quarters one predicted length each: the
+// renderer's mesh-only loop, unspilled, with and without TRAIN.
+constexpr bool HasRunMap(bool renderer_source, bool mesh, bool spill) { return HasTrain(renderer_source, mesh, spill); }
+
 }  // namespace ptv

@@ -194,6 +194,18 @@ class BasicRenderer(Handle):
         use, 1 octant or 2 length (ptGetBasicRendererRayOrder)."""
         return dict(zip(("order", "used"), hip_get("ptGetBasicRendererRayOrder", self._h, types=(U32, U32))))
 
+    def set_block_map(self, block_map: int):
+        """Which extend block traces which ray positions
+        (ptSetBasicRendererBlockMap): 0 automatic, 1 tile (a tile's four
+        quarters), 2 run (one quarter of four neighbouring tiles, under LENGTH
+        order).  Results are identical under every map."""
+        hip("ptSetBasicRendererBlockMap", self._h, int(block_map))
+
+    def block_map(self) -> dict:
+        """{map, used}: the map set (0 automatic) and the one the next rounds
+        use, 1 tile or 2 run (ptGetBasicRendererBlockMap)."""
+        return dict(zip(("map", "used"), hip_get("ptGetBasicRendererBlockMap", self._h, types=(U32, U32))))
+
     def ray_positions(self) -> np.ndarray:
         """Per slot, the position of its ray (high byte) and of its last hit
         (low byte) within its tile (diagnostic, ptReadBasicRendererRayPositions)."""
@@ -304,4 +316,5 @@ class BasicRenderer(Handle):
         hip("ptGetBasicRendererShadeInfo", self._h, C.byref(info))
         return {"scene_mask": int(info.scene_mask), "kernel_mask": int(info.kernel_mask),
                 "completion_queue": bool(info.completion_queue), "grey_records": bool(info.grey_records),
-                "ray_order": int(info.ray_order), "length_trained": bool(info.length_trained)}
+                "ray_order": int(info.ray_order), "length_trained": bool(info.length_trained),
+                "block_map": int(info.block_map)}

@@ -20,6 +20,14 @@ length (DESIGN.md §4 "Length classes").  CPU only.
    long as its longest ray), SIMD efficiency = lane steps / (64 x wave steps),
    and the distinct node / face records a tile's waves fetch, wave by wave.
 
+4. Block maps (DESIGN.md §4 "Block map"; include/pt_blockmap.h): which four
+   waves share an extend block -- a tile's four (TILE), or wave j of four
+   tiles: consecutive in the row-major tile index (RUN), a 2 x 2 quad, or
+   four consecutive tiles of a t % 3 tile group (3 apart).  A block holds its
+   four wave slots until its longest wave ends: block slot-steps = 4 x the
+   longest wave, filled = wave steps / slot-steps, and the distinct records
+   the block's 256 rays fetch.
+
 usage: python tools/exp_lenclass.py [--tiles 128] [--first 9] [--last 12] [--cells 8]
 """
 import argparse
@@ -167,6 +175,40 @@ def score(order_key, steps, recs):
     return ws / tiles, ls / (64.0 * ws), distinct / tiles
 
 
+def tile_waves(order_key):
+    """Per tile (row-major), its four waves' pixels in the given order."""
+    out = []
+    for by in range(H // 16):
+        for bx in range(W // 16):
+            pix = np.array([(by * 16 + y) * W + bx * 16 + x for y in range(16) for x in range(16)])
+            pix = pix[np.argsort(order_key[pix], kind="stable")]
+            out.append([pix[w * 64:(w + 1) * 64] for w in range(4)])
+    return out
+
+
+def block_maps():
+    """name -> the groups of tiles whose wave j shares a block (None: a tile's own four waves)."""
+    T, tx = (W // 16) * (H // 16), W // 16
+    return [("one tile's four waves", None),
+            ("wave j of four tiles next to each other in a row", [list(range(u, min(u + 4, T))) for u in range(0, T, 4)]),
+            ("wave j of a 2x2 quad of tiles", [[(y + dy) * tx + x + dx for dy in (0, 1) for dx in (0, 1)]
+                                               for y in range(0, H // 16, 2) for x in range(0, tx, 2)]),
+            ("wave j of four tiles taken 3 apart", [list(range(g + 12 * u, min(g + 12 * u + 12, T), 3))
+                                                    for g in range(3) for u in range((T + 11) // 12) if g + 12 * u < T])]
+
+
+def block_score(waves, groups, steps, recs):
+    """(wave steps, block slot-steps, filled, distinct records per block) of one block map."""
+    if groups is None:
+        blocks = [w for w in waves]
+    else:
+        blocks = [[waves[t][j] for t in g] for g in groups for j in range(4)]
+    ws = sum(int(steps[p].max()) for b in blocks for p in b)
+    slot = sum(4 * max(int(steps[p].max()) for p in b) for b in blocks)
+    records = sum(len(np.unique(np.concatenate([recs[i] for p in b for i in p]))) for b in blocks)
+    return ws, slot, ws / slot, records / len(blocks)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--first", type=int, default=9)
@@ -200,6 +242,17 @@ def main():
     base = scores[1][0]   # against the production order
     for (name, _), (ws, eff, dist) in zip(rows, scores):
         print(f"{name:58s} wave steps/tile {ws:6.1f} ({ws / base - 1:+.1%})  SIMD eff {eff:.3f}  distinct records/tile {dist:6.0f}")
+    # Block maps, for the OCTANT and the LENGTH order.
+    length = next(key for name, key in rows if "(LENGTH)" in name)
+    base = None
+    print("block maps (all tiles of the frame):")
+    for order, key in (("OCTANT", octant), ("LENGTH", length)):
+        waves = tile_waves(key)
+        for name, groups in block_maps():
+            ws, slot, filled, records = block_score(waves, groups, steps, recs)
+            base = base or (ws, slot)
+            print(f"{order + ', ' + name:58s} wave steps {ws:6d} ({ws / base[0] - 1:+.1%})  block slot-steps {slot:6d} "
+                  f"({slot / base[1] - 1:+.1%})  filled {filled:.3f}  records/block {records:5.0f}")
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
-"""Compare the device code of two builds kernel by kernel.
+r"""Compare the device code of two builds kernel by kernel.
 
-usage: python tools/kernel_diff.py A B [hipcc flags...]
+usage: python tools/kernel_diff.py [--rename-b REGEX REPL] A B [hipcc flags...]
 
 A and B are each a source tree (its path-tracer_amd/csrc/hip/*.hip are
 compiled device-only for the offload architecture, with the flags of this
@@ -16,6 +16,12 @@ Prints the kernels of each side by family, then the kernels present on one
 side only, the kernels defined more than once on a side, and the kernels whose
 body or metadata differ.  Exit status 1 if any of those lists is not empty.
 The tool compares; it does not look for any instruction or pattern.
+
+--rename-b: B's kernel names pass through re.sub(REGEX, REPL) before the two
+sides are paired -- for a change that adds a template parameter, so that the
+instantiations without the new flag meet their parent's (a trailing bool:
+--rename-b '^(_ZN3ptd13extend_kernel.*)Lb0E(EEvNS_6dscene)' '\1\2' pairs
+extend_kernel<..., false> with the parent's extend_kernel<...>).
 """
 from __future__ import annotations
 
@@ -126,12 +132,24 @@ def family(mangled: str) -> str:
 
 
 def main():
+    rename = None
+    if len(sys.argv) > 3 and sys.argv[1] == "--rename-b":
+        rename = (re.compile(sys.argv[2]), sys.argv[3])
+        del sys.argv[1:4]
     if len(sys.argv) < 3:
         sys.exit(__doc__)
     a, b, extra = Path(sys.argv[1]), Path(sys.argv[2]), sys.argv[3:]
     with tempfile.TemporaryDirectory(prefix="kernel_diff_a_") as ta, tempfile.TemporaryDirectory(prefix="kernel_diff_b_") as tb:
         ka, twice_a, la = side(a, Path(ta), extra)
         kb, twice_b, lb = side(b, Path(tb), extra)
+    if rename:
+        renamed = {}
+        for k, v in kb.items():
+            n = rename[0].sub(rename[1], k)
+            if n in renamed:
+                twice_b.append(n)
+            renamed[n] = v
+        kb = renamed
     print(f"A = {a}: {len(ka)} kernels\n" + "\n".join(la))
     print(f"B = {b}: {len(kb)} kernels\n" + "\n".join(lb))
     only_a, only_b = sorted(set(ka) - set(kb)), sorted(set(kb) - set(ka))

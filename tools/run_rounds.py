@@ -26,6 +26,8 @@ def main():
     ap.add_argument("--split", type=int, default=0, help="tile groups (ptSetBasicRendererSplit; 0 automatic, 1 off)")
     ap.add_argument("--ray-order", type=int, default=0,
                     help="ptSetBasicRendererRayOrder (0 automatic, 1 octant, 2 length); needs a build that has it")
+    ap.add_argument("--block-map", type=int, default=0,
+                    help="ptSetBasicRendererBlockMap (0 automatic, 1 tile, 2 run); needs a build that has it")
     a = ap.parse_args()
     if a.lib:
         os.environ["PT_HIP_LIB"] = str((ROOT / a.lib) if not os.path.isabs(a.lib) else a.lib)
@@ -44,6 +46,8 @@ def main():
     r.set_split(a.split)
     if a.ray_order:
         r.set_ray_order(a.ray_order)
+    if a.block_map:
+        r.set_block_map(a.block_map)
     r.RenderFlags = info.render_flags
     r.PathTerminationProbability = info.termination_probability
     r.reset()
