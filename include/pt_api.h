@@ -36,7 +36,10 @@
  * which keeps a frame's history across a camera move
  * (ptReprojectSampleBufferMoving: and across an object move), and rounds on a
  * chosen set of 16 x 16 tiles (ptSetBasicRendererActiveTiles) with the
- * per-tile statistics that choose them (ptComputeTileStatistics).
+ * per-tile statistics that choose them (ptComputeTileStatistics), and an
+ * any-hit occlusion query (ptOccludedRays: one bit per ray, equal to "the
+ * closest-hit query hits") with an ambient-occlusion / sky-visibility image
+ * built on it (ptRenderAmbientOcclusion).
  *
  * Conventions: creators return NULL on failure and set ptGetLastError();
  * other calls return 0 on success or a non-zero status (HIP / RCCL error
@@ -102,14 +105,14 @@ typedef struct pt_pixel_state {
 
 enum {
     PT_KERNEL_RAYGEN  = 0,
-    PT_KERNEL_EXTEND  = 1,
+    PT_KERNEL_EXTEND  = 1,   /* also ptTraceRays' extend launch and ptOccludedRays' launch */
     PT_KERNEL_SHADE   = 2,
     PT_KERNEL_RESOLVE = 3,
     PT_KERNEL_PREVIEW = 4,
     PT_KERNEL_ROUND   = 5,   /* fused extend + shade of a small partition (one launch per round) */
     PT_KERNEL_ROUNDS  = 6,   /* a round batch: several rounds of every tile in one launch */
     PT_KERNEL_DENOISE = 7,   /* one a-trous iteration of ptDenoiseSampleBuffer; ptDespikeSampleBuffer's launch */
-    PT_KERNEL_GUIDES  = 8,   /* ptRenderDenoiseGuides */
+    PT_KERNEL_GUIDES  = 8,   /* ptRenderDenoiseGuides[Specular], ptRenderAmbientOcclusion */
     PT_KERNEL_STATS   = 9,   /* ptComputeFrameStatistics' and ptComputeTileStatistics' passes, ptAccumulateSampleBuffer's add */
     PT_KERNEL_REPROJECT = 10, /* ptReprojectSampleBuffer, ptReprojectSampleBufferMoving, ptRectifyHistory */
     PT_KERNEL_COUNT   = 11,
@@ -706,6 +709,25 @@ int  ptSetFrameStatisticsVariant(pt_device* device, uint32_t variant);
 int ptTraceRays(pt_device* device, pt_scene* scene, uint32_t n, const float* origins,
                 const uint32_t* packed_velocities, const float* durations, pt_hit_record* out);
 
+/* The any-hit (occlusion) query (no reference counterpart; DESIGN.md §6 row
+ * 14): for each of ptTraceRays' n rays, whether anything lies within its
+ * duration.  mask holds (n + 63) / 64 words; ray i is bit i % 64 of word
+ * i / 64, and the bits at and above n in the last word are 0.  Every word is
+ * written.  The traversal is Trace() stopped at its first accepted
+ * intersection, a prefix of the closest-hit traversal of the same ray, so
+ *     occluded(ray) == (ptTraceRays(ray).shape_material != 0xFFFFFFFF)
+ * holds exactly, for every ray, duration, stack format and scene.  A hit at
+ * exactly `duration` counts or not as the shape's own test decides (a plane,
+ * sphere or mesh face at t == duration occludes, a cube does not): it is
+ * Trace()'s rule, not one of this query's.  No hit record is formed and there
+ * is no finalize pass: one launch, one bit per ray read back.  Blocks, like
+ * ptTraceRays, and fails as it does: on a NULL device or scene, on n > 0 with
+ * a NULL array, on a scene without packs; n == 0 succeeds and writes nothing.
+ * While the device profiles, the launch is timed under PT_KERNEL_EXTEND, as
+ * ptTraceRays' extend launch is. */
+int ptOccludedRays(pt_device* device, pt_scene* scene, uint32_t n, const float* origins,
+                   const uint32_t* packed_velocities, const float* durations, uint64_t* mask);
+
 /* Diagnostic: evaluates the device's exact fast division helper (XDiv: an
  * FMA-corrected reciprocal, no longer on the traversal path since the slab
  * test's reciprocal convention) against IEEE division on n
@@ -757,6 +779,33 @@ int ptExtendStepCounts(pt_device* device, pt_basic_renderer* renderer, uint32_t*
 int ptTraceRaysStats(pt_device* device, pt_scene* scene, uint32_t n, const float* origins,
                      const uint32_t* packed_velocities, const float* durations,
                      uint64_t out[PT_EXTEND_STATS_COUNT], uint32_t* steps);
+/* Diagnostic: the same counters and step counts for ptOccludedRays' any-hit
+ * traversal of those rays (the first nine counters are filled).  A ray's
+ * any-hit step count is at most its closest-hit one, and equal where the ray
+ * is not occluded. */
+int ptOccludedRaysStats(pt_device* device, pt_scene* scene, uint32_t n, const float* origins,
+                        const uint32_t* packed_velocities, const float* durations,
+                        uint64_t out[PT_EXTEND_STATS_COUNT], uint32_t* steps);
+
+/* Ambient occlusion / sky visibility (no reference counterpart; definition in
+ * pt_visibility.h and DESIGN.md §6 row 14).  Every pixel of dst takes the
+ * primary ray and normal of ptRenderDenoiseGuides for camera camera_index; on
+ * a hit, params->Samples cosine-lobe rays of length params->Radius leave the
+ * hit point, drawn from the integrator's random stream of that pixel in frame
+ * params->Seed, and go through the any-hit traversal of ptOccludedRays.  The
+ * pixel becomes (u, u, u, Samples) with u the number of unoccluded rays; a
+ * miss, or a camera of unknown model, is (Samples, Samples, Samples, Samples).
+ * dst is therefore an accumulator: ptRenderSampleBuffer shows the visible
+ * fraction, ptAccumulateSampleBuffer adds images of different seeds, and both
+ * denoisers take it.  .y is the value; the image is data, not colour (the
+ * three equal components are not CIE XYZ of anything).  Enqueues one launch
+ * (counted under PT_KERNEL_GUIDES) and returns, like ptRenderDenoiseGuides;
+ * two calls give the same bits.  Fails, launching and writing nothing, on a
+ * NULL argument, a scene or buffer of another device, a scene without packs,
+ * camera_index out of range, Samples outside 1..64 or a Radius that is not
+ * > 0 (a NaN included). */
+int ptRenderAmbientOcclusion(pt_device* device, pt_scene* scene, uint32_t camera_index,
+                             const pt_ambient_occlusion_parameters* params, pt_sample_buffer* dst);
 
 /* Per-kernel device time, measured with HIP events on the renderer stream. */
 int ptSetProfiling(pt_device* device, int enable);

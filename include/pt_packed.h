@@ -255,6 +255,15 @@ typedef struct pt_despike_parameters {
     float    NormalCosine;             /* in (-1, 1], default 0.9: smallest dot product with a member's normal */
 } pt_despike_parameters;
 
+/* Ambient occlusion / sky visibility (arithmetic in
+ * pt_visibility.h): how many cosine-lobe rays leave a pixel's primary hit, how
+ * far an occluder may lie and which random stream draws them. */
+typedef struct pt_ambient_occlusion_parameters {
+    uint32_t Samples;                  /* 1..64, default 16: rays per pixel */
+    float    Radius;                   /* > 0, default +inf; at or beyond PT_HIT_TIME_LIMIT (+inf): visibility of the sky */
+    uint32_t Seed;                     /* default 0: the integrator's FrameIndex of the stream the rays are drawn from */
+} pt_ambient_occlusion_parameters;
+
 /* One shape's motion between two packed scenes, filled
  * by ptsShapeMotion (pt_scene.h) and read by the moving-shape reprojection
  * (pt_reproject.h).  Point: rows 0..2 of the affine map from the current
@@ -320,6 +329,7 @@ static_assert(sizeof(pt_denoise_pair_parameters) == 20, "denoise_pair_parameters
 static_assert(sizeof(pt_reproject_parameters) == 16, "reproject_parameters");
 static_assert(sizeof(pt_rectify_parameters) == 20, "rectify_parameters");
 static_assert(sizeof(pt_despike_parameters) == 24, "despike_parameters");
+static_assert(sizeof(pt_ambient_occlusion_parameters) == 12, "ambient_occlusion_parameters");
 static_assert(sizeof(pt_shape_motion) == 96, "shape_motion");
 static_assert(sizeof(pt_packed_transform) == 128, "packed_transform");
 static_assert(sizeof(pt_packed_texture) == 32, "packed_texture");

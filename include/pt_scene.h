@@ -269,6 +269,16 @@ int  ptsDespike(uint32_t width, uint32_t height, const float* accum, const pt_de
  * or an unknown camera model. */
 int  ptsCentralCameraRay(const pt_packed_camera* camera, uint32_t x, uint32_t y, uint32_t width, uint32_t height,
                          float origin[3], float velocity[3]);
+/* pt_visibility.h's sample rays of pixel (x, y) on the host (DESIGN.md §6 row
+ * 14; what ptRenderAmbientOcclusion (pt_api.h) traces, bit for bit): the
+ * pixel's primary ray (origin, velocity) hit at `time` a surface whose guide
+ * normal is `normal`; out_origins receives 3 * Samples floats, out_velocities
+ * the Samples packed velocities, and *out_duration, if not NULL, the rays'
+ * duration.  Non-zero, writing nothing, on a NULL argument (out_duration
+ * excepted) or parameters outside their range (pt_packed.h). */
+int  ptsAmbientOcclusionRays(const pt_ambient_occlusion_parameters* params, uint32_t x, uint32_t y,
+                             const float origin[3], const float velocity[3], float time, const float normal[3],
+                             float* out_origins, uint32_t* out_velocities, float* out_duration);
 
 /* Frame statistics on the host (no reference counterpart; definition in
  * DESIGN.md §6 row 6, arithmetic in pt_stats.h): the CPU path for saved

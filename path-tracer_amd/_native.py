@@ -143,6 +143,19 @@ class pt_despike_parameters(C.Structure):
 
 assert C.sizeof(pt_despike_parameters) == 24
 
+
+class pt_ambient_occlusion_parameters(C.Structure):
+    """pt_ambient_occlusion_parameters (include/pt_packed.h)."""
+    _fields_ = [
+        ("Samples", C.c_uint32),
+        ("Radius", C.c_float),
+        ("Seed", C.c_uint32),
+    ]
+
+
+assert C.sizeof(pt_ambient_occlusion_parameters) == 12
+AMBIENT_OCCLUSION_MAX_SAMPLES = 64   # PT_AMBIENT_OCCLUSION_MAX_SAMPLES (include/pt_visibility.h)
+
 STATS_BINS = 256
 
 
@@ -365,6 +378,8 @@ SCENE_API = {
     "ptsRectifyHistory": (_i32, [_u32, _u32, _fptr, _fptr, _vp, C.POINTER(pt_rectify_parameters), _fptr]),
     "ptsDespike": (_i32, [_u32, _u32, _fptr, _vp, C.POINTER(pt_despike_parameters), _fptr]),
     "ptsCentralCameraRay": (_i32, [C.POINTER(pt_packed_camera), _u32, _u32, _u32, _u32, _fptr, _fptr]),
+    "ptsAmbientOcclusionRays": (_i32, [C.POINTER(pt_ambient_occlusion_parameters), _u32, _u32, _fptr, _fptr, _f32,
+                                       _fptr, _fptr, _u32ptr, _fptr]),
     "ptsFrameStatistics": (_i32, [_u32, _u32, _fptr, _fptr, C.POINTER(pt_frame_statistics)]),
     "ptsTileStatistics": (_i32, [_u32, _u32, _fptr, _fptr, _f32, _vp]),
     "ptsStatsBin": (_i32, [C.c_float]),
@@ -439,6 +454,9 @@ HIP_API = {
     "ptRenderFrame": (_i32, [_vp, _vp, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     "ptReadBasicRendererState": (_i32, [_vp, _vp, _vp]),
     "ptTraceRays": (_i32, [_vp, _vp, _u32, _fptr, _u32ptr, _fptr, _vp]),
+    "ptOccludedRays": (_i32, [_vp, _vp, _u32, _fptr, _u32ptr, _fptr, C.POINTER(C.c_uint64)]),
+    "ptOccludedRaysStats": (_i32, [_vp, _vp, _u32, _fptr, _u32ptr, _fptr, C.POINTER(C.c_uint64), _vp]),
+    "ptRenderAmbientOcclusion": (_i32, [_vp, _vp, _u32, C.POINTER(pt_ambient_occlusion_parameters), _vp]),
     "ptCreatePreviewRenderContext": (_vp, [_vp, _vp]),
     "ptDestroyPreviewRenderContext": (None, [_vp, _vp]),
     "ptRenderPreview": (_i32, [_vp, _vp, C.POINTER(pt_preview_parameters)]),

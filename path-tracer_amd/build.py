@@ -22,7 +22,7 @@ SCENE_SRC = sorted((CSRC / "scene").glob("*.cpp"))
 SCENE_HDR = sorted((CSRC / "scene").glob("*.hpp")) + sorted(INCLUDE.glob("*.h"))
 # The slowest to compile first: one object per source, compiled concurrently.
 HIP_SRC = [CSRC / "hip" / f"{name}.hip" for name in (
-    "shade", "rounds", "extend", "kernels", "resolve", "preview", "denoise", "stats", "reproject", "rectify",
+    "shade", "rounds", "extend", "occlusion", "kernels", "resolve", "preview", "denoise", "stats", "reproject", "rectify",
     "despike", "probe", "rt_rounds", "rt_scene", "rt_post", "rt_renderer", "rt_probe", "rt_comm", "rt_device",
     "rt_buffer")]
 HIP_HDR = sorted((CSRC / "hip").glob("*.hpp")) + sorted(INCLUDE.glob("*.h"))

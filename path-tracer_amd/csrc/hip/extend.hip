@@ -208,11 +208,17 @@ hipError_t pt_launch_extend(const ptd::dscene& S, const ptd::dslots& L, const pt
     return LaunchExtend(S, ptd::ray_source_slots{U, F}, L.n, unit_count, spill, train, true, st);
 }
 
+hipError_t pt_launch_trace_rays_extend(const ptd::dscene& S, uint32_t n, const float* origins, const uint32_t* vel,
+                                       const float* dur, float4* hit, float2* hc, uint32_t* spill, hipStream_t st)
+{
+    return LaunchExtend(S, ptd::ray_source_arrays{origins, vel, dur, hit, hc}, n, Blocks(n), spill, false, false, st);
+}
+
 hipError_t pt_launch_trace_rays(const ptd::dscene& S, uint32_t n, const float* origins, const uint32_t* vel,
                                 const float* dur, float4* hit, float2* hc, float4* rec, float2* uv, uint32_t* spill,
                                 hipStream_t st)
 {
-    hipError_t e = LaunchExtend(S, ptd::ray_source_arrays{origins, vel, dur, hit, hc}, n, Blocks(n), spill, false, false, st);
+    hipError_t e = pt_launch_trace_rays_extend(S, n, origins, vel, dur, hit, hc, spill, st);
     if (e != hipSuccess) return e;
     return pt_launch_finalize(S, n, hit, hc, rec, uv, st);
 }

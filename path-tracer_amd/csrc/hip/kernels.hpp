@@ -287,6 +287,27 @@ hipError_t pt_launch_trace_rays_stats(const ptd::dscene& S, uint32_t n, const fl
 hipError_t pt_launch_trace_rays(const ptd::dscene& S, uint32_t n, const float* origins, const uint32_t* vel,
                                 const float* dur, float4* hit, float2* hc, float4* rec, float2* uv, uint32_t* spill,
                                 hipStream_t st);
+// ptTraceRays' first launch alone: Trace() of the arrays' rays -> compact hits.
+hipError_t pt_launch_trace_rays_extend(const ptd::dscene& S, uint32_t n, const float* origins, const uint32_t* vel,
+                                       const float* dur, float4* hit, float2* hc, uint32_t* spill, hipStream_t st);
+// The any-hit query (occlusion.hip) over ptTraceRays'
+// inputs: mask word i / 64, bit i % 64 = "something lies within ray i's
+// duration"; every one of the (n + 63) / 64 words is written, the last one's
+// tail bits 0.  spill as for pt_launch_trace_rays.  The stats form fills
+// ptExtendStats' counters (out, cleared by the caller) and, if steps is not
+// null, each ray's step count.
+hipError_t pt_launch_occluded_rays(const ptd::dscene& S, uint32_t n, const float* origins, const uint32_t* vel,
+                                   const float* dur, uint32_t* spill, unsigned long long* mask, hipStream_t st);
+hipError_t pt_launch_occluded_rays_stats(const ptd::dscene& S, uint32_t n, const float* origins, const uint32_t* vel,
+                                         const float* dur, uint32_t* spill, unsigned long long* out, uint32_t* steps,
+                                         hipStream_t st);
+// The ambient-occlusion image (occlusion.hip; include/pt_visibility.h): one
+// pixel per thread in 16 x 16 tiles -> out (w x h, {u, u, u, Samples}).  spill:
+// (needed - pt_extend_stack_cap()) rows of tiles * 256 columns, or null.  p has
+// passed pt_visibility_parameters_ok.
+hipError_t pt_launch_ambient_occlusion(const ptd::dscene& S, uint32_t camera_index, uint32_t w, uint32_t h,
+                                       const pt_ambient_occlusion_parameters* p, uint32_t* spill, float4* out,
+                                       hipStream_t st);
 hipError_t pt_launch_finalize(const ptd::dscene& S, uint32_t n, const float4* hit, const float2* hc, float4* rec,
                               float2* uv, hipStream_t st);
 uint32_t pt_extend_stack_cap();

@@ -2,6 +2,7 @@
 // preview, denoise guides, the denoisers, reprojection, history validation, the
 // firefly clamp, statistics and accumulation.
 #include "runtime.hpp"
+#include "../../../include/pt_visibility.h"
 
 #include <initializer_list>
 #include <string>
@@ -204,6 +205,39 @@ int ptRenderDenoiseGuidesSpecular(pt_device* d, pt_scene* s, pt_denoise_guides* 
                                   uint32_t max_bounces)
 {
     return RenderGuides(d, s, g, camera_index, true, max_bounces);
+}
+
+// --- ambient occlusion / sky visibility (occlusion.hip) --------
+
+// One launch, counted under PT_KERNEL_GUIDES (the same launch shape: a primary
+// ray per pixel in 16 x 16 tiles).  The spill rows are the scene's, grown on
+// demand (a regrowth frees the old rows, which waits for the device).
+int ptRenderAmbientOcclusion(pt_device* d, pt_scene* s, uint32_t camera_index, const pt_ambient_occlusion_parameters* p,
+                             pt_sample_buffer* dst)
+{
+    if (!d || !s || !p || !dst) { SetError("null argument"); return -1; }
+    if (s->dev != d || dst->dev != d) { SetError("ambient occlusion: scene or sample buffer of another device"); return -1; }
+    if (!s->valid) { SetError("ambient occlusion: scene has no valid packs (call ptUpdateScene)"); return -1; }
+    if (camera_index >= s->camera_count) {
+        SetError("ambient occlusion: camera index %u out of range (%u cameras)", camera_index, s->camera_count);
+        return -1;
+    }
+    if (!pt_visibility_parameters_ok(p)) {
+        SetError("ambient occlusion: Samples %u (1..%u) or Radius %g (> 0) out of range", p->Samples,
+                 (uint32_t)PT_AMBIENT_OCCLUSION_MAX_SAMPLES, (double)p->Radius);
+        return -1;
+    }
+    PT_HIP(hipSetDevice(d->id));
+    const uint32_t need = s->stack_needed, cap = pt_extend_stack_cap();
+    uint32_t* spill = nullptr;
+    if (need > cap) {
+        const size_t threads = (size_t)((dst->width + 15) / 16) * ((dst->height + 15) / 16) * 256;
+        PT_HIP(s->visibility_spill.alloc((need - cap) * threads));
+        spill = s->visibility_spill.ptr;
+    }
+    PT_TIMED(d, PT_KERNEL_GUIDES,
+             pt_launch_ambient_occlusion(s->d, camera_index, dst->width, dst->height, p, spill, dst->accum, d->stream));
+    return 0;
 }
 
 int ptReadDenoiseGuides(pt_device* d, pt_denoise_guides* g, pt_denoise_guide* out)

@@ -165,6 +165,7 @@ struct pt_scene {
     bool len_trained = false;    // a finalize has written len_cls since the last clear
     bool len_pending = false;    // training rounds ran since the last finalize
     uint64_t len_rounds = 0;     // LENGTH rounds issued since the last clear (the training schedule's clock)
+    ptrt::dbuf<uint32_t> visibility_spill;   // ptRenderAmbientOcclusion's spill rows (deep scenes only; grown on demand)
     bool valid = false;
 };
 

@@ -100,4 +100,16 @@ constexpr bool HasTrain(bool renderer_source, bool mesh, bool spill) { return re
 // renderer's mesh-only loop, unspilled, with and without TRAIN.
 constexpr bool HasRunMap(bool renderer_source, bool mesh, bool spill) { return HasTrain(renderer_source, mesh, spill); }
 
+// --- occlusion ----------------------------------------------------------------------
+
+// The any-hit kernel (occlusion.hip) takes extend's stack entry, spill and
+// mesh-only choices as they are.  Its LDS node cache rides where extend's
+// does; PT_OCCLUSION_NODE_CACHE=0 (tools/build_variant.py) builds it without,
+// for the comparison in DESIGN.md §6 row 14.
+#ifndef PT_OCCLUSION_NODE_CACHE
+#define PT_OCCLUSION_NODE_CACHE 1
+#endif
+template <class E>
+constexpr bool HasOcclusionNodeCache(bool spill) { return PT_OCCLUSION_NODE_CACHE != 0 && HasNodeCache<E>(spill); }
+
 }  // namespace ptv

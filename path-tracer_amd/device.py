@@ -149,6 +149,28 @@ class DeviceScene(Handle):
         hip("ptTraceRays", self.device.handle, self._h, len(v), N.fptr(o), N.u32ptr(v), N.fptr(d), out.ctypes.data)
         return out
 
+    def occluded(self, origins: np.ndarray, packed_velocities: np.ndarray, durations: np.ndarray) -> np.ndarray:
+        """The any-hit query (ptOccludedRays): per ray of
+        a trace_rays batch, whether anything lies within its duration.  A bool
+        array equal to trace_rays(...)["shape_material"] != 0xFFFFFFFF, from
+        one launch and one bit per ray read back."""
+        o, v, d = _ray_batch(origins, packed_velocities, durations)
+        n = len(v)
+        words = np.zeros((n + 63) // 64, dtype=np.uint64)
+        hip("ptOccludedRays", self.device.handle, self._h, n, N.fptr(o), N.u32ptr(v), N.fptr(d),
+            words.ctypes.data_as(C.POINTER(C.c_uint64)))
+        return np.unpackbits(words.view(np.uint8), bitorder="little")[:n].astype(bool)
+
+    def occluded_stats(self, origins: np.ndarray, packed_velocities: np.ndarray, durations: np.ndarray):
+        """trace_rays_stats' counters and per-ray step counts for the any-hit
+        traversal of the batch (diagnostic, ptOccludedRaysStats)."""
+        o, v, d = _ray_batch(origins, packed_velocities, durations)
+        out = (C.c_uint64 * 14)()
+        steps = np.zeros(len(v), dtype=np.uint32)
+        hip("ptOccludedRaysStats", self.device.handle, self._h, len(v), N.fptr(o), N.u32ptr(v), N.fptr(d), out,
+            steps.ctypes.data)
+        return extend_stats(out, 9), steps
+
     def sample_textures(self, texture_index: np.ndarray, uv: np.ndarray, wrap: int = 0) -> np.ndarray:
         """Test probe (ptSampleTextures): SampleTexture of the uploaded scene
         at (n, 2) UVs; wrap 0 = remainder, 1 = the lean kernel's two-select

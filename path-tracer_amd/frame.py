@@ -11,8 +11,8 @@ from . import _native as N
 from ._core import Handle, PathTracerError, camera_struct, hip, motion_table, tile_grid
 from .device import Device, DeviceScene
 from .host import FrameStatistics, shape_motion
-from .params import (DenoiseParameters, DenoisePairParameters, DespikeParameters, RectifyParameters,
-                     ReprojectParameters, ResolveParameters)
+from .params import (AmbientOcclusionParameters, DenoiseParameters, DenoisePairParameters, DespikeParameters,
+                     RectifyParameters, ReprojectParameters, ResolveParameters)
 
 
 class DenoiseGuides(Handle):
@@ -192,6 +192,19 @@ class SampleBuffer(Handle):
         """This accumulator += src's, per component in float32, on the device
         (ptAccumulateSampleBuffer; enqueues).  src is not written."""
         hip("ptAccumulateSampleBuffer", self.device.handle, self._h, src.handle)
+
+    def render_ambient_occlusion(self, device_scene: "DeviceScene", camera_index: int = 0, samples: int = 16,
+                                 radius: float = float("inf"), seed: int = 0,
+                                 params: "AmbientOcclusionParameters | None" = None):
+        """The ambient-occlusion / sky-visibility image of packed camera
+        `camera_index` into this buffer (ptRenderAmbientOcclusion; enqueues):
+        every pixel becomes (u, u, u, samples), u of its `samples` cosine-lobe
+        rays of length `radius` from the primary hit being unoccluded (a miss:
+        u = samples).  An accumulator: render() shows the visible fraction,
+        accumulate() adds images of other seeds, the denoisers take it.  The
+        value is .y; the image is data, not colour.  DESIGN.md §6 row 14."""
+        p = (params or AmbientOcclusionParameters(samples, radius, seed)).as_struct()
+        hip("ptRenderAmbientOcclusion", self.device.handle, device_scene.handle, int(camera_index), C.byref(p), self._h)
 
     def read_resolved(self) -> np.ndarray:
         """OutColor of the last render(): (H, W, 4) float32, alpha 1."""

@@ -18,8 +18,8 @@ from .device import Comm, Device, DeviceScene, device_count
 from .frame import DenoiseGuides, FrameHistory, SampleBuffer
 from .host import (FrameStatistics, denoise_host, denoise_pair_host, despike_host, frame_statistics_host,
                    rectify_host, reproject_host, shape_motion, tile_mask_of_region, tile_statistics_host)
-from .params import (DenoiseParameters, DenoisePairParameters, DespikeParameters, RectifyParameters,
-                     ReprojectParameters, ResolveParameters)
+from .params import (AmbientOcclusionParameters, DenoiseParameters, DenoisePairParameters, DespikeParameters,
+                     RectifyParameters, ReprojectParameters, ResolveParameters)
 from .preview import PreviewParameters, PreviewRenderContext
 from .renderer import REFINE_MIN_ROUNDS, BasicRenderer, refine_tiles, render_until_noise
 

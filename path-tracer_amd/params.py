@@ -126,3 +126,18 @@ class DespikeParameters:
         # Out-of-range counts reach the library's check instead of ctypes' wrap-around.
         u = [min(max(v, 0), 0xFFFFFFFF) for v in (self.Radius, self.Rank, self.MinNeighbours)]
         return N.pt_despike_parameters(u[0], u[1], u[2], self.Scale, self.Floor, self.NormalCosine)
+
+
+class AmbientOcclusionParameters:
+    """pt_ambient_occlusion_parameters (pt_packed.h): the rays per pixel of
+    the ambient-occlusion image (Samples, 1..64), how far an occluder may lie
+    (Radius > 0; inf: visibility of the sky) and the integrator frame whose
+    random stream draws them (Seed).  DESIGN.md §6 row 14."""
+
+    def __init__(self, Samples: int = 16, Radius: float = float("inf"), Seed: int = 0):
+        self.Samples, self.Radius, self.Seed = int(Samples), float(Radius), int(Seed)
+
+    def as_struct(self) -> N.pt_ambient_occlusion_parameters:
+        # An out-of-range count reaches the library's check instead of ctypes' wrap-around.
+        return N.pt_ambient_occlusion_parameters(min(max(self.Samples, 0), 0xFFFFFFFF), self.Radius,
+                                                 self.Seed & 0xFFFFFFFF)

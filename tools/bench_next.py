@@ -49,6 +49,13 @@
   1024x1024, C5 at 2048x1024 (both cameras) and C3 at 1920x1080 (nothing to
   follow), with the share of followed pixels and the mean chain length;
   every figure three times.
+* occlusion (ptOccludedRays and ptRenderAmbientOcclusion, occlusion.hip;
+  DESIGN.md §6 row 14): kernel ms of the any-hit launch beside ptTraceRays'
+  extend launch on the same rays in the same run -- the live rays of a
+  1920x1080 renderer on C2, C3 and C5 after 4 rounds, and random rays -- with
+  the occluded share and the step ratio; and the ambient-occlusion image at
+  1920x1080 with 1, 4 and 16 samples beside ptRenderDenoiseGuides of the same
+  run; every figure three times.
 * tiles (ptComputeTileStatistics, stats.hip, and ptSetBasicRendererActiveTiles;
   DESIGN.md §6 row 10): kernel ms of the per-tile statistics launch, single
   and pair, beside ptComputeFrameStatistics on the same buffers in the same
@@ -61,7 +68,7 @@
   on all of the job's threads, and the RGB -> spectrum table.
 
 Kernel times are HIP events on the device stream (ptGetKernelStats).
-Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|rectify|despike|specular_guides|preview|openpbr|host ...]
+Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|rectify|despike|specular_guides|occlusion|preview|openpbr|host ...]
 (default: all).
 """
 import json
@@ -623,6 +630,72 @@ def specular_guides(pt, dev):
     return out
 
 
+def occlusion(pt, dev):
+    """rays: per ray set the kernel ms of ptOccludedRays' launch (any_hit_ms)
+    and of ptTraceRays' extend launch (closest_hit_ms) on the same rays in the
+    same run (HIP events around the launches; uploads, the finalize pass and
+    the read-backs are outside them), each a list: the mean of 5 timed calls
+    after a warm-up call, taken three times in turn; with the share of
+    occluded rays and the any-hit / closest-hit step ratio of the diagnostic
+    twins.  The sets: the live rays of a 1920x1080 renderer on C2, C3 and C5
+    after 4 rounds, in image order, and rays.random_rays on each.
+    image: ptRenderAmbientOcclusion at 1920x1080, Samples 1, 4 and 16,
+    infinite radius, beside ptRenderDenoiseGuides of the same run (both under
+    PT_KERNEL_GUIDES), on C2, C3 and C5; per_sample_ms = (ms at 16 - ms at 1)
+    / 15."""
+    from rays import random_rays
+    out = {"rays": {}, "image": {}}
+    W, H = 1920, 1080
+    for cid in (2, 3, 5):
+        scene = pt.Scene.config(cid)
+        ds = pt.DeviceScene(dev)
+        ds.update(scene)
+        sb = pt.SampleBuffer(dev, W, H)
+        r = pt.BasicRenderer(dev, ds, sb)
+        r.RenderFlags = 3
+        r.reset()
+        r.run(4)
+        dev.synchronize()
+        st = r.read_state().reshape(-1)
+        r.close()
+        live = (np.ascontiguousarray(st["origin"]), np.ascontiguousarray(st["packed_velocity"]),
+                np.full(len(st), 1048576.0, np.float32))
+        for name, (o, v, d) in (("renderer", live), ("random", random_rays(scene.arrays(), 1 << 20, 7))):
+            res = {"rays": len(v), "extend_form": ds.extend_form, "any_hit_ms": [], "closest_hit_ms": []}
+            mask = ds.occluded(o, v, d)
+            res["occluded_share"] = round(float(mask.mean()), 4)
+            k = slice(0, 1 << 16)
+            sa, sc = ds.occluded_stats(o[k], v[k], d[k])[1], ds.trace_rays_stats(o[k], v[k], d[k])[1]
+            res["step_ratio"] = round(float(sa.sum()) / max(float(sc.sum()), 1.0), 4)
+            runs = {"any_hit_ms": lambda: ds.occluded(o, v, d), "closest_hit_ms": lambda: ds.trace_rays(o, v, d)}
+            for _ in range(3):
+                for key, fn in runs.items():
+                    fn()   # warm
+                    ms, _ = timed(dev, K_EXTEND, fn, 5)
+                    res[key].append(round(ms, 4))
+            out["rays"][f"c{cid}_{name}"] = res
+        guides = pt.DenoiseGuides(dev, W, H)
+        runs = {"guides_ms": lambda: guides.render(ds, 0)}
+        for s in (1, 4, 16):
+            runs[f"samples{s}_ms"] = lambda s=s: sb.render_ambient_occlusion(ds, samples=s)
+        res = {"pixels": W * H}
+        for key in runs:
+            res[key] = []
+        for _ in range(3):
+            for key, fn in runs.items():
+                fn()   # warm
+                ms, _ = timed(dev, K_GUIDES, fn, 5)
+                res[key].append(round(ms, 4))
+        res["per_sample_ms"] = [round((a - b) / 15.0, 4) for a, b in zip(res["samples16_ms"], res["samples1_ms"])]
+        img = sb.read()
+        res["visible_share"] = round(float(img[..., 1].sum() / img[..., 3].sum()), 4)
+        out["image"][f"c{cid}_{W}x{H}"] = res
+        for x in (guides, sb, ds):
+            x.close()
+        scene.close()
+    return out
+
+
 def preview(pt, dev):
     out = {}
     modes = {"base_color": pt.PREVIEW_RENDER_MODE_BASE_COLOR, "shaded": pt.PREVIEW_RENDER_MODE_BASE_COLOR_SHADED,
@@ -703,7 +776,7 @@ def host_builds(pt):
 def main():
     pt = load()
     entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "tiles": tiles, "reproject": reproject, "reproject_moving": reproject_moving,
-               "rectify": rectify, "despike": despike, "specular_guides": specular_guides,
+               "rectify": rectify, "despike": despike, "specular_guides": specular_guides, "occlusion": occlusion,
                "preview": preview, "openpbr": openpbr}
     want = sys.argv[1:] or list(entries) + ["host"]
     dev = pt.Device(0)
