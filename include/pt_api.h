@@ -39,7 +39,9 @@
  * per-tile statistics that choose them (ptComputeTileStatistics), and an
  * any-hit occlusion query (ptOccludedRays: one bit per ray, equal to "the
  * closest-hit query hits") with an ambient-occlusion / sky-visibility image
- * built on it (ptRenderAmbientOcclusion).
+ * built on it (ptRenderAmbientOcclusion), and the same lobe gathered at
+ * caller-given points: an occlusion count, mask and bent vector per point
+ * (ptGatherVisibility).
  *
  * Conventions: creators return NULL on failure and set ptGetLastError();
  * other calls return 0 on success or a non-zero status (HIP / RCCL error
@@ -105,7 +107,7 @@ typedef struct pt_pixel_state {
 
 enum {
     PT_KERNEL_RAYGEN  = 0,
-    PT_KERNEL_EXTEND  = 1,   /* also ptTraceRays' extend launch and ptOccludedRays' launch */
+    PT_KERNEL_EXTEND  = 1,   /* also ptTraceRays' extend launch, ptOccludedRays' launch and ptGatherVisibility's launches */
     PT_KERNEL_SHADE   = 2,
     PT_KERNEL_RESOLVE = 3,
     PT_KERNEL_PREVIEW = 4,
@@ -806,6 +808,35 @@ int ptOccludedRaysStats(pt_device* device, pt_scene* scene, uint32_t n, const fl
  * > 0 (a NaN included). */
 int ptRenderAmbientOcclusion(pt_device* device, pt_scene* scene, uint32_t camera_index,
                              const pt_ambient_occlusion_parameters* params, pt_sample_buffer* dst);
+
+/* Visibility gathered at caller-given points (no reference counterpart;
+ * definition in pt_visibility.h and DESIGN.md §6 row 15): for light probes,
+ * vertex or texel bakes and contact shading, where the points are not the
+ * pixels of a camera.  points and normals hold 3 floats per point and are
+ * used as given (a normal is neither normalised nor quantised).  Point i
+ * draws params->Samples rays of row 14's cosine lobe around its normal from
+ * the random stream params->FirstIndex + i of frame params->Seed; they start
+ * params->Offset along their direction, reach params->Radius and go through
+ * ptOccludedRays' any-hit traversal, one lane per (point, sample).  out[i] is
+ * the point's pt_visibility_record (pt_packed.h): the occluded bits, the
+ * unoccluded count and the bent vector, summed by a fixed tree, so two calls
+ * give the same bits.  A point's first S' rays are its rays at Samples = S',
+ * and a call on points [a, b) with FirstIndex = a equals that slice of the
+ * whole call.  Uploads 24 bytes per point, launches in chunks of whole points
+ * and at most 2^22 lanes (each launch counted under PT_KERNEL_EXTEND), reads
+ * back 32 bytes per point and blocks.  n == 0 succeeds and touches nothing.
+ * Fails, launching and writing nothing, on a NULL argument (the arrays with
+ * n > 0), a scene of another device or without packs, Samples not a power of
+ * two in 1..64, a Radius that is not > 0 (a NaN included), an Offset that is
+ * negative or not finite, n > 2^26 or FirstIndex + n > 2^32. */
+int ptGatherVisibility(pt_device* device, pt_scene* scene, uint32_t n, const float* points, const float* normals,
+                       const pt_visibility_gather_parameters* params, pt_visibility_record* out);
+/* Test probe: ptGatherVisibility with launches of at most max_lanes lanes
+ * (64..2^22; ptGatherVisibility passes 2^22), so that a small batch takes
+ * several launches.  The records do not depend on max_lanes. */
+int ptGatherVisibilityChunked(pt_device* device, pt_scene* scene, uint32_t n, const float* points,
+                              const float* normals, const pt_visibility_gather_parameters* params,
+                              uint32_t max_lanes, pt_visibility_record* out);
 
 /* Per-kernel device time, measured with HIP events on the renderer stream. */
 int ptSetProfiling(pt_device* device, int enable);

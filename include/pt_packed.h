@@ -264,6 +264,29 @@ typedef struct pt_ambient_occlusion_parameters {
     uint32_t Seed;                     /* default 0: the integrator's FrameIndex of the stream the rays are drawn from */
 } pt_ambient_occlusion_parameters;
 
+/* Visibility gathered at caller-given points (arithmetic
+ * in pt_visibility.h): row 14's cosine lobe around each point's normal, and
+ * which random stream each point draws from. */
+typedef struct pt_visibility_gather_parameters {
+    uint32_t Samples;                  /* 1, 2, 4, 8, 16, 32 or 64, default 16: rays per point */
+    float    Radius;                   /* > 0, default +inf; at or beyond PT_HIT_TIME_LIMIT (+inf): visibility of the sky */
+    uint32_t Seed;                     /* default 0: the integrator's FrameIndex of the streams the rays are drawn from */
+    float    Offset;                   /* finite, >= 0, default 1e-3: a ray starts at P + Offset * W */
+    uint32_t FirstIndex;               /* default 0: point i draws from stream FirstIndex + i; FirstIndex + n <= 2^32 */
+} pt_visibility_gather_parameters;
+
+/* One point's answer.  Bit k of OccludedMask: the point's ray k found
+ * something within its duration (bits at and above Samples are 0).  Bent: the
+ * sum of the traced velocities of the unoccluded rays, by the fixed pairwise
+ * tree of pt_visibility_reduce. */
+typedef struct pt_visibility_record {
+    float    Bent[3];
+    float    Unoccluded;               /* Samples - popcount(OccludedMask) */
+    uint64_t OccludedMask;
+    float    Samples;
+    uint32_t Reserved;                 /* 0 */
+} pt_visibility_record;
+
 /* One shape's motion between two packed scenes, filled
  * by ptsShapeMotion (pt_scene.h) and read by the moving-shape reprojection
  * (pt_reproject.h).  Point: rows 0..2 of the affine map from the current
@@ -330,6 +353,8 @@ static_assert(sizeof(pt_reproject_parameters) == 16, "reproject_parameters");
 static_assert(sizeof(pt_rectify_parameters) == 20, "rectify_parameters");
 static_assert(sizeof(pt_despike_parameters) == 24, "despike_parameters");
 static_assert(sizeof(pt_ambient_occlusion_parameters) == 12, "ambient_occlusion_parameters");
+static_assert(sizeof(pt_visibility_gather_parameters) == 20, "visibility_gather_parameters");
+static_assert(sizeof(pt_visibility_record) == 32, "visibility_record");
 static_assert(sizeof(pt_shape_motion) == 96, "shape_motion");
 static_assert(sizeof(pt_packed_transform) == 128, "packed_transform");
 static_assert(sizeof(pt_packed_texture) == 32, "packed_texture");

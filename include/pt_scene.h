@@ -279,6 +279,25 @@ int  ptsCentralCameraRay(const pt_packed_camera* camera, uint32_t x, uint32_t y,
 int  ptsAmbientOcclusionRays(const pt_ambient_occlusion_parameters* params, uint32_t x, uint32_t y,
                              const float origin[3], const float velocity[3], float time, const float normal[3],
                              float* out_origins, uint32_t* out_velocities, float* out_duration);
+/* The rays of ptGatherVisibility (pt_api.h) on the host,
+ * bit for bit, point-major: ray i * Samples + k is sample k of point i.
+ * points, normals: 3 floats per point.  out_origins receives 3 floats per ray,
+ * out_velocities the packed velocities and out_durations the durations, n *
+ * Samples rays.  Non-zero, writing nothing, on a NULL argument (the arrays
+ * with n > 0) or parameters outside their range (pt_packed.h; n <= 2^26). */
+int  ptsGatherVisibilityRays(const pt_visibility_gather_parameters* params, uint32_t n, const float* points,
+                             const float* normals, float* out_origins, uint32_t* out_velocities,
+                             float* out_durations);
+/* ptGatherVisibility's records from a one-bit-per-ray answer over those rays
+ * (ptOccludedRays' mask layout: ray r is bit r % 64 of word r / 64), with the
+ * device's summation tree.  packed: the rays' packed velocities.  Non-zero,
+ * writing nothing, on samples not a power of two in 1..64, n > 2^26 or a NULL
+ * array with n > 0. */
+int  ptsGatherVisibilityReduce(uint32_t samples, uint32_t n, const uint32_t* packed, const uint64_t* occluded_bits,
+                               pt_visibility_record* out);
+/* pt_visibility_skip as a library call: `state` after `steps` steps of the
+ * random stream's generator. */
+uint32_t ptsVisibilitySkip(uint32_t state, uint32_t steps);
 
 /* Frame statistics on the host (no reference counterpart; definition in
  * DESIGN.md §6 row 6, arithmetic in pt_stats.h): the CPU path for saved

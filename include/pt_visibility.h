@@ -107,4 +107,123 @@ PT_HD uint32_t pt_visibility_ray(const pt_visibility_frame* F, pt3 O, pt3 V, flo
     return pt_reproject_pack_unit(W);
 }
 
+/* --- visibility gathered at caller-given points ---------
+ *
+ * The device kernel is visibility_gather_kernel (csrc/hip/occlusion.hip), the
+ * host twins ptsGatherVisibilityRays / ptsGatherVisibilityReduce
+ * (csrc/scene/visibility.cpp), the numpy restatement
+ * tests/gather_restatement.py.
+ *
+ * Point i of n, position P and normal N as given (neither normalised nor
+ * quantised), parameters {Samples S, Radius, Seed, Offset, FirstIndex}:
+ *
+ *   j  = FirstIndex + i
+ *   s0 = pt_seed(j & 0xFFFF, j >> 16, Seed)   (injective in (x < 65536, y): the
+ *            points' streams do not collide)
+ *   frame: F.N = N; X, Y as pt_visibility_make_frame derives them from F.N
+ *   sample k = 0 .. S-1:
+ *     state = s0 advanced by 2 k steps of pt_random's LCG (pt_visibility_skip)
+ *     D = RandomDirection(state); L = SafeNormalize(D + (0, 0, 1))
+ *     W = (L.x X + L.y Y) + L.z N
+ *     ray k: origin P + Offset W (multiply, then add, per component), velocity
+ *            unpack(pack(W)), duration pt_visibility_duration(Radius)
+ *   occ_k = whether anything lies within ray k's duration
+ *   record (pt_visibility_record): OccludedMask bit k = occ_k; Unoccluded =
+ *     S - popcount; Samples = S; Reserved = 0; Bent = the component-wise
+ *     pairwise sum of b_k = occ_k ? (0, 0, 0) : velocity_k, b'_m = b_2m +
+ *     b_2m+1 for log2 S levels (float addition is commutative, so the tree
+ *     has one result whichever operand a lane holds).
+ *
+ * A point's first S' rays are the rays of Samples = S' (nesting), and a call
+ * on points [a, b) with FirstIndex = a equals that slice of the whole call
+ * (partition independence). */
+
+#define PT_VISIBILITY_GATHER_MAX_POINTS (1u << 26)
+#define PT_VISIBILITY_GATHER_MAX_LANES (1u << 22)   /* (point, sample) pairs of one launch */
+
+/* Samples a power of two in 1..64; Radius > 0 (a NaN is not); Offset finite and
+ * >= 0; n <= 2^26 and FirstIndex + n <= 2^32. */
+PT_HD int pt_visibility_gather_parameters_ok(const pt_visibility_gather_parameters* p, uint32_t n)
+{
+    const uint32_t S = p->Samples;
+    if (S < 1u || S > PT_AMBIENT_OCCLUSION_MAX_SAMPLES || (S & (S - 1u)) != 0u) return 0;
+    if (!(p->Radius > 0.0f)) return 0;
+    if (!(p->Offset >= 0.0f && p->Offset <= 3.402823466e+38f)) return 0;
+    if (n > PT_VISIBILITY_GATHER_MAX_POINTS) return 0;
+    return (uint64_t)p->FirstIndex + (uint64_t)n <= 4294967296ull;
+}
+
+/* `state` after `steps` steps of pt_random's LCG (x -> 747796405 x +
+ * 2891336453 mod 2^32), in log2(steps) rounds: the composition of affine maps
+ * by repeated squaring, all in exact arithmetic mod 2^32, so it equals
+ * sequential stepping bit for bit. */
+PT_HD uint32_t pt_visibility_skip(uint32_t state, uint32_t steps)
+{
+    uint32_t a = 747796405u, c = 2891336453u;   /* the map of 2^r steps */
+    uint32_t A = 1u, C = 0u;                    /* the map of the steps taken so far */
+    while (steps != 0u) {
+        if (steps & 1u) {
+            A = A * a;
+            C = C * a + c;
+        }
+        c = (a + 1u) * c;
+        a = a * a;
+        steps >>= 1u;
+    }
+    return A * state + C;
+}
+
+PT_HD uint32_t pt_visibility_gather_seed(uint32_t j, uint32_t Seed) { return pt_seed(j & 0xFFFFu, j >> 16u, Seed); }
+
+/* The frame around a point's normal, used as given: pt_visibility_make_frame's
+ * X and Y around F.N = N. */
+PT_HD pt_visibility_frame pt_visibility_gather_frame(pt3 N)
+{
+    pt_visibility_frame F;
+    F.N = N;
+    const pt3 A = pt_abs(F.N.x) < 0.9f ? v3(1, 0, 0) : v3(0, 1, 0);
+    F.X = normalize(cross(A, F.N));
+    F.Y = cross(F.X, F.N);
+    return F;
+}
+
+/* Sample k of the point at P whose stream starts at s0: its origin, and its
+ * velocity as the packed word (the velocity traced is pt_reproject_unpack_unit
+ * of the word). */
+PT_HD uint32_t pt_visibility_gather_ray(const pt_visibility_frame* F, pt3 P, float Offset, uint32_t s0, uint32_t k,
+                                        pt3* RO)
+{
+    uint32_t state = pt_visibility_skip(s0, 2u * k);
+    const pt3 D = pt_visibility_random_direction(&state);
+    const pt3 L = pt_visibility_safe_normalize(D + v3(0, 0, 1));
+    const pt3 W = (L.x * F->X + L.y * F->Y) + L.z * F->N;
+    *RO = P + Offset * W;
+    return pt_reproject_pack_unit(W);
+}
+
+/* A point's record from its S packed velocities and its occluded bits: the
+ * tree the device kernel's cross-lane rounds form. */
+PT_HD pt_visibility_record pt_visibility_reduce(uint32_t S, const uint32_t* packed, uint64_t occluded)
+{
+    pt3 b[PT_AMBIENT_OCCLUSION_MAX_SAMPLES];
+    uint32_t count = 0u;
+    b[0] = v3(0, 0, 0);
+    for (uint32_t k = 0; k < S; k++) {
+        const int occ = (int)((occluded >> k) & 1u);
+        count += (uint32_t)occ;
+        b[k] = occ ? v3(0, 0, 0) : pt_reproject_unpack_unit(packed[k]);
+    }
+    for (uint32_t w = S; w > 1u; w >>= 1u)
+        for (uint32_t m = 0; m < w / 2u; m++) b[m] = b[2u * m] + b[2u * m + 1u];
+    pt_visibility_record R;
+    R.Bent[0] = b[0].x;
+    R.Bent[1] = b[0].y;
+    R.Bent[2] = b[0].z;
+    R.Unoccluded = (float)(S - count);
+    R.OccludedMask = S < 64u ? occluded & ((1ull << S) - 1ull) : occluded;
+    R.Samples = (float)S;
+    R.Reserved = 0u;
+    return R;
+}
+
 #endif /* PT_VISIBILITY_H */

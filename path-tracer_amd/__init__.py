@@ -20,7 +20,8 @@ from .integrator import (Device, DeviceScene, SampleBuffer, BasicRenderer, Comm,
                          render_until_noise, DenoisePairParameters, denoise_pair_host, ReprojectParameters,
                          reproject_host, FrameHistory, shape_motion, tile_statistics_host, tile_mask_of_region,
                          refine_tiles, REFINE_MIN_ROUNDS, RectifyParameters, rectify_host, DespikeParameters,
-                         despike_host, AmbientOcclusionParameters)
+                         despike_host, AmbientOcclusionParameters, VisibilityGatherParameters,
+                         gather_visibility_rays_host, gather_visibility_reduce_host, shape_surface_points)
 from ._native import (PREVIEW_RENDER_MODE_BASE_COLOR, PREVIEW_RENDER_MODE_BASE_COLOR_SHADED, PREVIEW_RENDER_MODE_NORMAL,
                       PREVIEW_RENDER_MODE_MATERIAL_INDEX, PREVIEW_RENDER_MODE_PRIMITIVE_INDEX,
                       PREVIEW_RENDER_MODE_MESH_COMPLEXITY, PREVIEW_RENDER_MODE_SCENE_COMPLEXITY)
@@ -33,6 +34,7 @@ from ._native import KERNEL_STATS, STATS_BINS, STATS_VARIANT_AUTO, STATS_VARIANT
 from ._native import KERNEL_REPROJECT, CAMERA_DTYPE, TILE_SIZE, TILE_STATS_DTYPE
 from ._native import SHAPE_DTYPE, SHAPE_MOTION_DTYPE, SHAPE_MOTION_MOVED, SHAPE_MOTION_NO_HISTORY
 from ._native import AMBIENT_OCCLUSION_MAX_SAMPLES
+from ._native import VISIBILITY_RECORD_DTYPE, VISIBILITY_GATHER_MAX_POINTS
 from .image import write_png, write_ppm, write_pfm, read_png
 from .layout import band_rows, owned_pixels
 

@@ -156,6 +156,26 @@ class pt_ambient_occlusion_parameters(C.Structure):
 assert C.sizeof(pt_ambient_occlusion_parameters) == 12
 AMBIENT_OCCLUSION_MAX_SAMPLES = 64   # PT_AMBIENT_OCCLUSION_MAX_SAMPLES (include/pt_visibility.h)
 
+
+class pt_visibility_gather_parameters(C.Structure):
+    """pt_visibility_gather_parameters (include/pt_packed.h)."""
+    _fields_ = [
+        ("Samples", C.c_uint32),
+        ("Radius", C.c_float),
+        ("Seed", C.c_uint32),
+        ("Offset", C.c_float),
+        ("FirstIndex", C.c_uint32),
+    ]
+
+
+assert C.sizeof(pt_visibility_gather_parameters) == 20
+# pt_visibility_record (include/pt_packed.h): one point's gathered visibility.
+VISIBILITY_RECORD_DTYPE = np.dtype([("Bent", "<f4", (3,)), ("Unoccluded", "<f4"), ("OccludedMask", "<u8"),
+                                    ("Samples", "<f4"), ("Reserved", "<u4")])
+assert VISIBILITY_RECORD_DTYPE.itemsize == 32
+VISIBILITY_GATHER_MAX_POINTS = 1 << 26   # PT_VISIBILITY_GATHER_MAX_POINTS (include/pt_visibility.h)
+VISIBILITY_GATHER_MAX_LANES = 1 << 22    # PT_VISIBILITY_GATHER_MAX_LANES
+
 STATS_BINS = 256
 
 
@@ -380,6 +400,10 @@ SCENE_API = {
     "ptsCentralCameraRay": (_i32, [C.POINTER(pt_packed_camera), _u32, _u32, _u32, _u32, _fptr, _fptr]),
     "ptsAmbientOcclusionRays": (_i32, [C.POINTER(pt_ambient_occlusion_parameters), _u32, _u32, _fptr, _fptr, _f32,
                                        _fptr, _fptr, _u32ptr, _fptr]),
+    "ptsGatherVisibilityRays": (_i32, [C.POINTER(pt_visibility_gather_parameters), _u32, _fptr, _fptr, _fptr, _u32ptr,
+                                       _fptr]),
+    "ptsGatherVisibilityReduce": (_i32, [_u32, _u32, _u32ptr, C.POINTER(C.c_uint64), _vp]),
+    "ptsVisibilitySkip": (_u32, [_u32, _u32]),
     "ptsFrameStatistics": (_i32, [_u32, _u32, _fptr, _fptr, C.POINTER(pt_frame_statistics)]),
     "ptsTileStatistics": (_i32, [_u32, _u32, _fptr, _fptr, _f32, _vp]),
     "ptsStatsBin": (_i32, [C.c_float]),
@@ -457,6 +481,9 @@ HIP_API = {
     "ptOccludedRays": (_i32, [_vp, _vp, _u32, _fptr, _u32ptr, _fptr, C.POINTER(C.c_uint64)]),
     "ptOccludedRaysStats": (_i32, [_vp, _vp, _u32, _fptr, _u32ptr, _fptr, C.POINTER(C.c_uint64), _vp]),
     "ptRenderAmbientOcclusion": (_i32, [_vp, _vp, _u32, C.POINTER(pt_ambient_occlusion_parameters), _vp]),
+    "ptGatherVisibility": (_i32, [_vp, _vp, _u32, _fptr, _fptr, C.POINTER(pt_visibility_gather_parameters), _vp]),
+    "ptGatherVisibilityChunked": (_i32, [_vp, _vp, _u32, _fptr, _fptr, C.POINTER(pt_visibility_gather_parameters),
+                                         _u32, _vp]),
     "ptCreatePreviewRenderContext": (_vp, [_vp, _vp]),
     "ptDestroyPreviewRenderContext": (None, [_vp, _vp]),
     "ptRenderPreview": (_i32, [_vp, _vp, C.POINTER(pt_preview_parameters)]),

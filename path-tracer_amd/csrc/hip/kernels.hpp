@@ -308,6 +308,14 @@ hipError_t pt_launch_occluded_rays_stats(const ptd::dscene& S, uint32_t n, const
 hipError_t pt_launch_ambient_occlusion(const ptd::dscene& S, uint32_t camera_index, uint32_t w, uint32_t h,
                                        const pt_ambient_occlusion_parameters* p, uint32_t* spill, float4* out,
                                        hipStream_t st);
+// Visibility gathered at n points (occlusion.hip; include/pt_visibility.h; DESIGN.md
+// §6 row 15): one lane per (point, sample), n * Samples <= 2^22 lanes -> out, two
+// float4 per point (pt_visibility_record).  Point i draws from stream first_index
+// + i.  spill: (needed - pt_extend_stack_cap()) rows of n * Samples columns, or
+// null.  p has passed pt_visibility_gather_parameters_ok.
+hipError_t pt_launch_gather_visibility(const ptd::dscene& S, uint32_t n, const float* points, const float* normals,
+                                       const pt_visibility_gather_parameters* p, uint32_t first_index, uint32_t* spill,
+                                       float4* out, hipStream_t st);
 hipError_t pt_launch_finalize(const ptd::dscene& S, uint32_t n, const float4* hit, const float2* hc, float4* rec,
                               float2* uv, hipStream_t st);
 uint32_t pt_extend_stack_cap();

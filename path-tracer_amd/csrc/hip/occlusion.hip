@@ -1,7 +1,7 @@
 // occlusion.hip — the any-hit query (no reference counterpart; DESIGN.md §6
 // row 14): whether anything lies within a ray's duration, one bit per ray, and
-// the ambient-occlusion / sky-visibility image built on it; with their
-// launchers.
+// the ambient-occlusion / sky-visibility image built on it, and the same lobe
+// gathered at caller-given points (row 15); with their launchers.
 //
 // The any-hit traversal is Trace() stopped at the first step that leaves an
 // accepted intersection in the lane (Hit.ShapeIndex set).  Until that step
@@ -228,6 +228,76 @@ __global__ __launch_bounds__(256) void ambient_occlusion_kernel(dscene S, ambien
     *px = make_float4(uf, uf, uf, Sf);
 }
 
+// --- visibility gathered at caller-given points --------------
+
+struct gather_args {
+    const float* points;    // 3 floats per point
+    const float* normals;   // 3 floats per point
+    uint32_t n;             // points of this launch; n << shift lanes are live
+    uint32_t shift;         // log2 of the samples per point
+    uint32_t seed;
+    uint32_t first;         // stream index of point 0
+    float offset;
+    float duration;
+};
+
+// A lane per (point, sample): the S lanes of a point are an aligned segment of
+// one wave (S is a power of two up to 64), so the point's mask is that
+// segment of the wave's ballot and its bent vector log2 S rounds of
+// __shfl_xor within it: no LDS, no atomics, one result whatever the order of
+// the lanes' arrival.  There is no primary trace to share, so a list of points
+// fills n S lanes where a lane per point would fill n.  Every lane reaches the
+// node-cache fill's barrier, the ballot and the shuffles: lanes at and beyond
+// n S trace nothing, vote 0 and add zeros in segments of their own.  Across the
+// trace a lane keeps its ray (ray_source_held) and the packed word; the
+// velocity is unpacked again for the sum.
+template <bool SPILL, int CAP, class E, bool NC, bool MESH>
+__global__ __launch_bounds__(256, 8) void visibility_gather_kernel(dscene S, gather_args P, uint32_t* spill,
+                                                                   uint32_t spill_stride, float4* __restrict__ out)
+{
+    __shared__ E smem[CAP * 256];
+    __shared__ float4 ncache[NC ? 4 * PT_NODE_CACHE_PAIRS : 1];
+    const uint32_t ncn = NC ? NodeCacheFill(S, ncache) : 0u;
+    const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t samples = 1u << P.shift;
+    const uint32_t point = g >> P.shift, k = g & (samples - 1u);
+    const bool live = point < P.n;
+    bool occluded = false;
+    uint32_t word = 0;
+    if (live) {
+        tstack<SPILL, CAP, E> st;
+        st.lds = &smem[threadIdx.x];
+        st.spill = spill + g;
+        st.stride = spill_stride;
+        st.nc = ncache;
+        st.ncn = ncn;
+        const float* p = P.points + 3 * (size_t)point;
+        const float* nrm = P.normals + 3 * (size_t)point;
+        const pt_visibility_frame F = pt_visibility_gather_frame(v3(nrm[0], nrm[1], nrm[2]));
+        pt3 RO;
+        word = pt_visibility_gather_ray(&F, v3(p[0], p[1], p[2]), P.offset,
+                                        pt_visibility_gather_seed(P.first + point, P.seed), k, &RO);
+        const ray_source_held cur{RO, pt_reproject_unpack_unit(word)};
+        no_stats ns;
+        occluded = AnyHit<SPILL, CAP, E, MESH>(S, st, cur, g, cur.O, cur.V, P.duration, ns);
+    }
+    const unsigned long long ballot = __ballot(occluded);
+    pt3 b = live && !occluded ? pt_reproject_unpack_unit(word) : v3(0, 0, 0);
+    for (uint32_t o = 1; o < samples; o <<= 1) {
+        b.x = b.x + __shfl_xor(b.x, (int)o, 64);
+        b.y = b.y + __shfl_xor(b.y, (int)o, 64);
+        b.z = b.z + __shfl_xor(b.z, (int)o, 64);
+    }
+    if (live && k == 0) {
+        const unsigned long long segment = ballot >> (threadIdx.x & 63u);
+        const unsigned long long mask = P.shift == 6u ? segment : segment & ((1ull << samples) - 1ull);
+        const float Sf = (float)samples;
+        out[2 * (size_t)point] = make_float4(b.x, b.y, b.z, Sf - (float)__popcll(mask));
+        reinterpret_cast<uint4*>(out)[2 * (size_t)point + 1] =
+            make_uint4((uint32_t)mask, (uint32_t)(mask >> 32), __float_as_uint(Sf), 0u);
+    }
+}
+
 }  // namespace ptd
 
 // --- launchers (called from rt_probe.hip and rt_post.hip) --------------------------
@@ -250,6 +320,37 @@ hipError_t pt_launch_occluded_rays(const ptd::dscene& S, uint32_t n, const float
                 if constexpr (!NC || ptv::HasOcclusionNodeCache<E>(SPILL))
                     hipLaunchKernelGGL((ptd::occlusion_kernel<SPILL, PT_EXTEND_CAP, E, NC, MESH>), dim3(Blocks(n)),
                                        dim3(256), 0, st, S, src, n, spill, n, mask);
+            },
+            spill != nullptr, cache, S.single_mesh != 0);
+    });
+    return hipGetLastError();
+}
+
+// visibility_gather_kernel's instantiation is occlusion_kernel's, chosen the same way.
+hipError_t pt_launch_gather_visibility(const ptd::dscene& S, uint32_t n, const float* points, const float* normals,
+                                       const pt_visibility_gather_parameters* p, uint32_t first_index, uint32_t* spill,
+                                       float4* out, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    ptd::gather_args P;
+    P.points = points;
+    P.normals = normals;
+    P.n = n;
+    P.shift = 0;
+    while ((1u << P.shift) < p->Samples) P.shift++;
+    P.seed = p->Seed;
+    P.first = first_index;
+    P.offset = p->Offset;
+    P.duration = pt_visibility_duration(p->Radius);
+    const uint32_t lanes = n << P.shift;
+    ptv::SelectStackEntry(S.stack16 != 0, [&](auto entry) {
+        using E = typename decltype(entry)::type;
+        const bool cache = S.node_cache && ptv::HasOcclusionNodeCache<E>(spill != nullptr);
+        ptv::SelectFlags(
+            [&](auto SPILL, auto NC, auto MESH) {
+                if constexpr (!NC || ptv::HasOcclusionNodeCache<E>(SPILL))
+                    hipLaunchKernelGGL((ptd::visibility_gather_kernel<SPILL, PT_EXTEND_CAP, E, NC, MESH>),
+                                       dim3(Blocks(lanes)), dim3(256), 0, st, S, P, spill, lanes, out);
             },
             spill != nullptr, cache, S.single_mesh != 0);
     });

@@ -2,6 +2,7 @@
 // counters, device numerics and the texture sampler, each checked against the
 // host by the tests.
 #include "runtime.hpp"
+#include "../../../include/pt_visibility.h"
 
 using namespace ptrt;
 
@@ -149,6 +150,56 @@ int ptOccludedRaysStats(pt_device* d, pt_scene* s, uint32_t n, const float* orig
     PT_HIP(hipStreamSynchronize(d->stream));
     for (int i = 0; i < PT_EXTEND_STATS_COUNT; i++) out[i] = h[i];
     return 0;
+}
+
+// Visibility gathered at caller-given points (occlusion.hip; DESIGN.md §6 row
+// 15).  A launch covers a whole number of points and at most max_lanes lanes,
+// which bounds a deep scene's spill rows at (stack_needed - cap) x max_lanes
+// words whatever n is.  Each launch is timed under PT_KERNEL_EXTEND.
+int ptGatherVisibilityChunked(pt_device* d, pt_scene* s, uint32_t n, const float* points, const float* normals,
+                              const pt_visibility_gather_parameters* params, uint32_t max_lanes,
+                              pt_visibility_record* out)
+{
+    if (!d || !s || !params || (n && (!points || !normals || !out))) { SetError("null argument"); return -1; }
+    if (s->dev != d) { SetError("ptGatherVisibility: scene of another device"); return -1; }
+    if (!s->valid) { SetError("scene has no valid packs"); return -1; }
+    if (!pt_visibility_gather_parameters_ok(params, n)) {
+        SetError("ptGatherVisibility: Samples %u (a power of two up to 64), Radius %g (> 0), Offset %g (finite, >= 0), "
+                 "FirstIndex %u + n %u (n <= 2^26, the sum <= 2^32)",
+                 params->Samples, (double)params->Radius, (double)params->Offset, params->FirstIndex, n);
+        return -1;
+    }
+    if (max_lanes < PT_AMBIENT_OCCLUSION_MAX_SAMPLES || max_lanes > PT_VISIBILITY_GATHER_MAX_LANES) {
+        SetError("ptGatherVisibilityChunked: max_lanes %u outside 64..2^22", max_lanes);
+        return -1;
+    }
+    if (n == 0) return 0;
+    PT_HIP(hipSetDevice(d->id));
+    const uint32_t chunk = std::min(n, max_lanes / params->Samples);   // points per launch, >= 1
+    const bool spill = s->stack_needed > pt_extend_stack_cap();
+    dbuf<float> d_p, d_n;
+    dbuf<uint32_t> d_spill;
+    dbuf<float4> d_out;
+    PT_HIP(d_p.upload(points, (size_t)n * 3));
+    PT_HIP(d_n.upload(normals, (size_t)n * 3));
+    PT_HIP(d_out.alloc((size_t)n * 2));
+    if (spill) PT_HIP(d_spill.alloc((size_t)(s->stack_needed - pt_extend_stack_cap()) * chunk * params->Samples));
+    for (uint32_t a = 0; a < n; a += chunk) {
+        const uint32_t m = std::min(chunk, n - a);
+        PT_TIMED(d, PT_KERNEL_EXTEND,
+                 pt_launch_gather_visibility(s->d, m, d_p.ptr + (size_t)a * 3, d_n.ptr + (size_t)a * 3, params,
+                                             params->FirstIndex + a, spill ? d_spill.ptr : nullptr,
+                                             d_out.ptr + (size_t)a * 2, d->stream));
+    }
+    PT_HIP(hipMemcpyAsync(out, d_out.ptr, (size_t)n * sizeof(pt_visibility_record), hipMemcpyDeviceToHost, d->stream));
+    PT_HIP(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+int ptGatherVisibility(pt_device* d, pt_scene* s, uint32_t n, const float* points, const float* normals,
+                       const pt_visibility_gather_parameters* params, pt_visibility_record* out)
+{
+    return ptGatherVisibilityChunked(d, s, n, points, normals, params, PT_VISIBILITY_GATHER_MAX_LANES, out);
 }
 
 int ptCheckFastDivision(pt_device* d, uint64_t n, uint32_t seed, uint64_t* mismatches)

@@ -24,3 +24,46 @@ extern "C" int ptsAmbientOcclusionRays(const pt_ambient_occlusion_parameters* pa
     if (out_duration) *out_duration = pt_visibility_duration(params->Radius);
     return 0;
 }
+
+// The gathered visibility of DESIGN.md §6 row 15 on the host, from the same
+// header: the rays visibility_gather_kernel traces, point-major, and the
+// records from any one-bit-per-ray answer over them.
+
+extern "C" int ptsGatherVisibilityRays(const pt_visibility_gather_parameters* params, uint32_t n, const float* points,
+                                       const float* normals, float* out_origins, uint32_t* out_velocities,
+                                       float* out_durations)
+{
+    if (!params || (n && (!points || !normals || !out_origins || !out_velocities || !out_durations))) return -1;
+    if (!pt_visibility_gather_parameters_ok(params, n)) return -1;
+    const uint32_t S = params->Samples;
+    const float duration = pt_visibility_duration(params->Radius);
+    for (uint32_t i = 0; i < n; i++) {
+        const pt3 P = v3(points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2]);
+        const pt_visibility_frame F =
+            pt_visibility_gather_frame(v3(normals[3 * (size_t)i], normals[3 * (size_t)i + 1], normals[3 * (size_t)i + 2]));
+        const uint32_t s0 = pt_visibility_gather_seed(params->FirstIndex + i, params->Seed);
+        for (uint32_t k = 0; k < S; k++) {
+            const size_t ray = (size_t)i * S + k;
+            pt3 RO;
+            out_velocities[ray] = pt_visibility_gather_ray(&F, P, params->Offset, s0, k, &RO);
+            out_origins[3 * ray] = RO.x; out_origins[3 * ray + 1] = RO.y; out_origins[3 * ray + 2] = RO.z;
+            out_durations[ray] = duration;
+        }
+    }
+    return 0;
+}
+
+extern "C" int ptsGatherVisibilityReduce(uint32_t samples, uint32_t n, const uint32_t* packed,
+                                         const uint64_t* occluded_bits, pt_visibility_record* out)
+{
+    if (samples < 1u || samples > PT_AMBIENT_OCCLUSION_MAX_SAMPLES || (samples & (samples - 1u)) != 0u) return -1;
+    if (n > PT_VISIBILITY_GATHER_MAX_POINTS || (n && (!packed || !occluded_bits || !out))) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        // Ray i S + k is bit (i S + k) % 64 of word (i S + k) / 64; S divides 64.
+        const size_t ray = (size_t)i * samples;
+        out[i] = pt_visibility_reduce(samples, packed + ray, occluded_bits[ray >> 6] >> (ray & 63u));
+    }
+    return 0;
+}
+
+extern "C" uint32_t ptsVisibilitySkip(uint32_t state, uint32_t steps) { return pt_visibility_skip(state, steps); }

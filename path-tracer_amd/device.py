@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _native as N
 from ._core import U32, U64, F64, Handle, extend_stats, hip, hip_get
+from .params import VisibilityGatherParameters
 
 if TYPE_CHECKING:
     from .frame import SampleBuffer
@@ -170,6 +171,29 @@ class DeviceScene(Handle):
         hip("ptOccludedRaysStats", self.device.handle, self._h, len(v), N.fptr(o), N.u32ptr(v), N.fptr(d), out,
             steps.ctypes.data)
         return extend_stats(out, 9), steps
+
+    def gather_visibility(self, points: np.ndarray, normals: np.ndarray, samples: int = 16,
+                          radius: float = float("inf"), seed: int = 0, offset: float = 1e-3, first_index: int = 0,
+                          params: "VisibilityGatherParameters | None" = None) -> np.ndarray:
+        """How open the hemisphere is at caller-given points (ptGatherVisibility;
+        DESIGN.md §6 row 15): mesh vertices, lightmap texels, probe positions.
+        points, normals: (n, 3); a normal is used as given.  Each point traces
+        `samples` rays (a power of two up to 64) of the ambient-occlusion
+        pass's cosine lobe around its normal, from `offset` along the ray to
+        `radius`, drawn from stream first_index + i of frame `seed`.  Returns n
+        VISIBILITY_RECORD_DTYPE records: OccludedMask (bit k: ray k is
+        blocked), Unoccluded (the open rays; / Samples is the visibility) and
+        Bent, the sum of the open rays' directions (normalise it for the bent
+        normal).  Blocks."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if len(p) != len(nrm):
+            raise ValueError(f"{len(p)} points and {len(nrm)} normals")
+        s = (params or VisibilityGatherParameters(samples, radius, seed, offset, first_index)).as_struct()
+        out = np.zeros(len(p), dtype=N.VISIBILITY_RECORD_DTYPE)
+        hip("ptGatherVisibility", self.device.handle, self._h, len(p), N.fptr(p), N.fptr(nrm), C.byref(s),
+            out.ctypes.data)
+        return out
 
     def sample_textures(self, texture_index: np.ndarray, uv: np.ndarray, wrap: int = 0) -> np.ndarray:
         """Test probe (ptSampleTextures): SampleTexture of the uploaded scene

@@ -9,7 +9,8 @@ import numpy as np
 
 from . import _native as N
 from ._core import camera_struct, guide_image, image, image_like, motion_table, pts, tile_grid
-from .params import DenoiseParameters, DenoisePairParameters, DespikeParameters, RectifyParameters, ReprojectParameters
+from .params import (DenoiseParameters, DenoisePairParameters, DespikeParameters, RectifyParameters, ReprojectParameters,
+                     VisibilityGatherParameters)
 
 
 class FrameStatistics:
@@ -220,6 +221,96 @@ def rectify_host(history: np.ndarray, current: np.ndarray, guides: np.ndarray,
     p = (params or RectifyParameters()).as_struct()
     pts("ptsRectifyHistory", a.shape[1], a.shape[0], N.fptr(a), N.fptr(b), g.ctypes.data, C.byref(p), N.fptr(out))
     return out
+
+
+def gather_visibility_rays_host(points: np.ndarray, normals: np.ndarray,
+                                params: "VisibilityGatherParameters | None" = None):
+    """The rays DeviceScene.gather_visibility traces, on the CPU
+    (ptsGatherVisibilityRays, libptscene.so: include/pt_visibility.h compiled
+    for the host), bit for bit.  points, normals: (n, 3).  Returns (origins
+    (n Samples, 3), packed velocities, durations), point-major: ray i Samples +
+    k is sample k of point i; the arguments of DeviceScene.occluded and
+    trace_rays."""
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    if len(p) != len(nrm):
+        raise ValueError(f"{len(p)} points and {len(nrm)} normals")
+    s = (params or VisibilityGatherParameters()).as_struct()
+    rays = len(p) * s.Samples if 1 <= s.Samples <= N.AMBIENT_OCCLUSION_MAX_SAMPLES else 0
+    o, v, d = np.zeros((rays, 3), np.float32), np.zeros(rays, np.uint32), np.zeros(rays, np.float32)
+    pts("ptsGatherVisibilityRays", C.byref(s), len(p), N.fptr(p), N.fptr(nrm), N.fptr(o), N.u32ptr(v), N.fptr(d))
+    return o, v, d
+
+
+def gather_visibility_reduce_host(samples: int, packed_velocities: np.ndarray, occluded: np.ndarray) -> np.ndarray:
+    """DeviceScene.gather_visibility's records from any answer to "is ray r
+    blocked" over gather_visibility_rays_host's rays (ptsGatherVisibilityReduce,
+    libptscene.so): the mask, the count and the bent vector by the device's
+    summation tree.  packed_velocities: (n samples,); occluded: one bool per
+    ray (DeviceScene.occluded's result, or a closest-hit query's "hit").
+    Returns n VISIBILITY_RECORD_DTYPE records."""
+    samples = int(samples)
+    v = np.ascontiguousarray(packed_velocities, dtype=np.uint32).reshape(-1)
+    occ = np.ascontiguousarray(occluded, dtype=bool).reshape(-1)
+    if samples < 1 or len(v) % samples or len(occ) != len(v):
+        raise ValueError(f"{len(v)} velocities and {len(occ)} bits for {samples} samples per point")
+    bits = np.zeros((len(v) + 63) // 64 * 8, np.uint8)
+    packed_bits = np.packbits(occ, bitorder="little")
+    bits[:len(packed_bits)] = packed_bits
+    out = np.zeros(len(v) // samples, dtype=N.VISIBILITY_RECORD_DTYPE)
+    pts("ptsGatherVisibilityReduce", samples, len(out), N.u32ptr(v), bits.view(np.uint64).ctypes.data_as(C.POINTER(C.c_uint64)),
+        out.ctypes.data)
+    return out
+
+
+def shape_surface_points(scene, shape_index: int):
+    """One world-space point and unit normal per vertex of packed mesh shape
+    `shape_index`, for baking visibility (DeviceScene.gather_visibility) on a
+    mesh without restating the packs.  scene: a packed Scene, or the dict of
+    its arrays().  The shape's packed mesh nodes are walked from
+    MeshRootNodeIndex; every distinct VertexIndex of the faces below gives one
+    entry, at its first occurrence: the face's position through the shape's
+    Transform.To, and the vertex's unpacked normal through the transpose of
+    From's 3 x 3, renormalised (the hit record's TransformNormal).  Returns
+    (points (n, 3) float32, normals (n, 3) float32, vertex indices (n,)
+    uint32)."""
+    a = scene if isinstance(scene, dict) else scene.arrays()
+    shapes = a["shapes"]
+    if not 0 <= int(shape_index) < len(shapes):
+        raise ValueError(f"shape index {shape_index} of {len(shapes)} shapes")
+    shape = shapes[int(shape_index)]
+    if int(shape["Type"]) != 0:   # PT_SHAPE_TYPE_MESH_INSTANCE
+        raise ValueError(f"shape {shape_index} of type {int(shape['Type'])} is not a mesh instance")
+    nodes, faces, vertices = a["mesh_nodes"], a["mesh_faces"], a["mesh_vertices"]
+    ranges, stack = [], [int(shape["MeshRootNodeIndex"])]
+    while stack:
+        node = nodes[stack.pop()]
+        begin, end = int(node["FaceBeginOrNodeIndex"]), int(node["FaceEndIndex"])
+        if end > 0:
+            ranges.append((begin, end))
+        else:
+            stack += [begin + 1, begin]
+    ranges.sort()
+    f = np.concatenate([faces[b:e] for b, e in ranges]) if ranges else faces[:0]
+    index = np.stack([f["VertexIndex0"], f["VertexIndex1"], f["VertexIndex2"]], axis=1).reshape(-1)
+    local = np.stack([f["Position0"], f["Position1"], f["Position2"]], axis=1).reshape(-1, 3).astype(np.float64)
+    index, first = np.unique(index, return_index=True)
+    local = local[first]
+    # The packed matrices are column-major: element (row r, column c) at [4 c + r].
+    to = shape["Transform"]["To"].astype(np.float64).reshape(4, 4).T
+    from_t = shape["Transform"]["From"].astype(np.float64).reshape(4, 4)[:3, :3]
+    points = local @ to[:3, :3].T + to[:3, 3]
+    # UnpackUnitVector (octahedral snorm16 x 2).
+    word = vertices["PackedNormal"][index]
+    p = np.stack([(word & 0xFFFF).astype(np.uint16).view(np.int16), (word >> 16).astype(np.uint16).view(np.int16)],
+                 axis=1).astype(np.float64) / 32767.0
+    p = np.clip(p, -1.0, 1.0)
+    z = 1.0 - np.abs(p[:, 0]) - np.abs(p[:, 1])
+    fold = (1.0 - np.abs(p[:, ::-1])) * np.where(p >= 0, 1.0, -1.0)
+    p = np.where((z < 0)[:, None], fold, p)
+    n = np.concatenate([p, z[:, None]], axis=1) @ from_t.T
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    return points.astype(np.float32), n.astype(np.float32), index.astype(np.uint32)
 
 
 def despike_host(accum: np.ndarray, guides: np.ndarray, params: "DespikeParameters | None" = None) -> np.ndarray:

@@ -141,3 +141,26 @@ class AmbientOcclusionParameters:
         # An out-of-range count reaches the library's check instead of ctypes' wrap-around.
         return N.pt_ambient_occlusion_parameters(min(max(self.Samples, 0), 0xFFFFFFFF), self.Radius,
                                                  self.Seed & 0xFFFFFFFF)
+
+
+class VisibilityGatherParameters:
+    """pt_visibility_gather_parameters (pt_packed.h): the rays per point of
+    DeviceScene.gather_visibility (Samples, a power of two up to 64), how far
+    an occluder may lie (Radius > 0; inf: visibility of the sky), the
+    integrator frame whose random streams draw them (Seed), how far along its
+    direction a ray starts (Offset, finite and >= 0; the default is the
+    integrator's restart offset) and the stream of the first point
+    (FirstIndex: point i draws from stream FirstIndex + i, so a batch cut in
+    pieces gives the whole batch's records).  DESIGN.md §6 row 15."""
+
+    def __init__(self, Samples: int = 16, Radius: float = float("inf"), Seed: int = 0, Offset: float = 1e-3,
+                 FirstIndex: int = 0):
+        self.Samples, self.Radius, self.Seed = int(Samples), float(Radius), int(Seed)
+        self.Offset, self.FirstIndex = float(Offset), int(FirstIndex)
+
+    def as_struct(self) -> N.pt_visibility_gather_parameters:
+        # An out-of-range count reaches the library's check instead of ctypes' wrap-around.
+        if not 0 <= self.FirstIndex <= 0xFFFFFFFF:
+            raise ValueError(f"FirstIndex {self.FirstIndex} outside 0..2^32 - 1")
+        return N.pt_visibility_gather_parameters(min(max(self.Samples, 0), 0xFFFFFFFF), self.Radius,
+                                                 self.Seed & 0xFFFFFFFF, self.Offset, self.FirstIndex)

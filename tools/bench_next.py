@@ -56,6 +56,12 @@
   the occluded share and the step ratio; and the ambient-occlusion image at
   1920x1080 with 1, 4 and 16 samples beside ptRenderDenoiseGuides of the same
   run; every figure three times.
+* gather (ptGatherVisibility, occlusion.hip): the summed
+  kernel ms of a call's launches beside ptOccludedRays' launch on the
+  identical point-major rays in the same run, on C2, C3 and C5 -- the primary
+  hits of the 1920x1080 guide image at 16 samples, and 1 024 of them at 64 --
+  with the wall time of the call beside the route without it (rays on the
+  host, ptOccludedRays, host reduce); every kernel figure three times.
 * tiles (ptComputeTileStatistics, stats.hip, and ptSetBasicRendererActiveTiles;
   DESIGN.md §6 row 10): kernel ms of the per-tile statistics launch, single
   and pair, beside ptComputeFrameStatistics on the same buffers in the same
@@ -68,7 +74,7 @@
   on all of the job's threads, and the RGB -> spectrum table.
 
 Kernel times are HIP events on the device stream (ptGetKernelStats).
-Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|rectify|despike|specular_guides|occlusion|preview|openpbr|host ...]
+Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|rectify|despike|specular_guides|occlusion|gather|preview|openpbr|host ...]
 (default: all).
 """
 import json
@@ -696,6 +702,120 @@ def occlusion(pt, dev):
     return out
 
 
+def guide_hit_points(pt, dev, ds, W, H):
+    """The primary hits of packed camera 0's W x H guide image as gather
+    points: P = O + t V along the pixel's central ray, N the guide normal
+    turned towards the camera.  The ray is formed here in float64 (a
+    measurement's points, not a parity check's), for the three camera models."""
+    guides = pt.DenoiseGuides(dev, W, H)
+    guides.render(ds, 0)
+    g = guides.read().reshape(-1)
+    guides.close()
+    cam = ds.cameras[0]
+    y, x = np.divmod(np.arange(W * H), W)
+    nx, ny = (x + 0.5) / W, (y + 0.5) / H
+    model = int(cam["Model"])
+    if model in (0, 1):
+        sp = np.stack([-float(cam["SensorSize"][0]) * (nx - 0.5), -float(cam["SensorSize"][1]) * (0.5 - ny),
+                       np.full(W * H, float(cam["SensorDistance"]))], axis=1)
+        v = -sp if model == 0 else -sp * float(cam["FocalLength"]) / (sp[:, 2:3] - float(cam["FocalLength"]))
+    else:
+        phi, theta = (nx - 0.5) * 2 * np.pi, (0.5 - ny) * np.pi
+        v = np.stack([np.cos(theta) * np.sin(phi), np.sin(theta), -np.cos(theta) * np.cos(phi)], axis=1)
+    v /= np.linalg.norm(v, axis=1, keepdims=True)
+    M = cam["Transform"]["To"].astype(np.float64).reshape(4, 4).T   # column-major in the pack
+    V = v @ M[:3, :3].T
+    hit = (g["shape"] != 0xFFFFFFFF) & np.isfinite(g["time"])
+    P = M[:3, 3] + g["time"][hit].astype(np.float64)[:, None] * V[hit]
+    Nr = g["normal"][hit].astype(np.float64)
+    Nr = np.where((np.einsum("ij,ij->i", Nr, V[hit]) > 0)[:, None], -Nr, Nr)
+    return np.ascontiguousarray(P, np.float32), np.ascontiguousarray(Nr, np.float32)
+
+
+def gather(pt, dev):
+    """Per config (C2, C3, C5) and point set -- guide_hits_s16: the primary
+    hits of the 1920x1080 guide image, 16 samples; probes_1024_s64: 1 024 of
+    them, evenly spaced, 64 samples -- gather_kernel_ms: the summed kernel
+    time of one ptGatherVisibility call's launches; occluded_kernel_ms:
+    ptOccludedRays' launch on the identical point-major rays
+    (ptsGatherVisibilityRays: the same rays at the same lanes) in the same
+    run, the stats reset between the legs; each a list: the mean of 3 timed
+    calls after a warm-up call, taken three times in turn.  kernel_ratio: the
+    ratio of the two medians; occluded_spread: (max - min) / median of the
+    comparator's own three figures.  occluded_chunked_kernel_ms (where a call
+    takes several launches): the comparator on the same rays in launches of
+    2^22, the gather call's chunks, which separates what the chunks' tails cost
+    from what making the rays in the kernel costs.  gather_wall_ms: the wall time of a
+    ptGatherVisibility call; route_*_ms: the wall time of the route without
+    it -- the rays on the host, ptOccludedRays (upload, launch, read-back,
+    unpacking the bits), the host reduce -- and their sum (once per run for
+    the large set, three times for the small one).  records_equal: the two
+    routes' records compared as bytes."""
+    out = {}
+    W, H = 1920, 1080
+    step = pt._native.VISIBILITY_GATHER_MAX_LANES
+
+    def leg(fn, reps):
+        dev.synchronize()
+        dev.reset_kernel_stats()
+        dev.set_profiling(True, period=1)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        dev.synchronize()
+        wall = time.perf_counter() - t0
+        n, ms = dev.kernel_stats(K_EXTEND)
+        dev.set_profiling(False)
+        return ms / reps, n // reps, wall / reps * 1e3
+
+    for cid in (2, 3, 5):
+        scene = pt.Scene.config(cid)
+        ds = pt.DeviceScene(dev)
+        ds.update(scene)
+        P, Nr = guide_hit_points(pt, dev, ds, W, H)
+        pick = np.linspace(0, len(P) - 1, 1024).astype(np.int64)
+        sets = {"guide_hits_s16": (P, Nr, 16, 1), "probes_1024_s64": (P[pick], Nr[pick], 64, 3)}
+        for name, (p, n, S, route_turns) in sets.items():
+            params = pt.VisibilityGatherParameters(S, float("inf"), 3)
+            res = {"points": len(p), "samples": S, "extend_form": ds.extend_form, "gather_kernel_ms": [],
+                   "occluded_kernel_ms": [], "gather_wall_ms": [], "route_rays_ms": [], "route_occluded_ms": [],
+                   "route_reduce_ms": [], "route_wall_ms": []}
+            for _ in range(route_turns):
+                t0 = time.perf_counter()
+                o, v, d = pt.gather_visibility_rays_host(p, n, params)
+                t1 = time.perf_counter()
+                occ = ds.occluded(o, v, d)
+                t2 = time.perf_counter()
+                ref = pt.gather_visibility_reduce_host(S, v, occ)
+                t3 = time.perf_counter()
+                for key, a, b in (("route_rays_ms", t0, t1), ("route_occluded_ms", t1, t2), ("route_reduce_ms", t2, t3),
+                                  ("route_wall_ms", t0, t3)):
+                    res[key].append(round((b - a) * 1e3, 3))
+            rec = ds.gather_visibility(p, n, params=params)   # warm
+            res["records_equal"] = bool(rec.tobytes() == ref.tobytes())
+            res["occluded_share"] = round(float(occ.mean()), 4)
+            res["launches_per_call"] = None
+            for _ in range(3):
+                ms, launches, wall = leg(lambda: ds.gather_visibility(p, n, params=params), 3)
+                res["gather_kernel_ms"].append(round(ms, 4))
+                res["gather_wall_ms"].append(round(wall, 3))
+                res["launches_per_call"] = launches
+                ms, _, _ = leg(lambda: ds.occluded(o, v, d), 3)
+                res["occluded_kernel_ms"].append(round(ms, 4))
+                if launches > 1:
+                    ms, _, _ = leg(lambda: [ds.occluded(o[a:a + step], v[a:a + step], d[a:a + step])
+                                            for a in range(0, len(v), step)], 3)
+                    res.setdefault("occluded_chunked_kernel_ms", []).append(round(ms, 4))
+            med = float(np.median(res["occluded_kernel_ms"]))
+            res["kernel_ratio"] = round(float(np.median(res["gather_kernel_ms"])) / med, 4)
+            res["occluded_spread"] = round((max(res["occluded_kernel_ms"]) - min(res["occluded_kernel_ms"])) / med, 4)
+            out[f"c{cid}_{name}"] = res
+            del o, v, d, occ
+        ds.close()
+        scene.close()
+    return out
+
+
 def preview(pt, dev):
     out = {}
     modes = {"base_color": pt.PREVIEW_RENDER_MODE_BASE_COLOR, "shaded": pt.PREVIEW_RENDER_MODE_BASE_COLOR_SHADED,
@@ -777,7 +897,7 @@ def main():
     pt = load()
     entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "tiles": tiles, "reproject": reproject, "reproject_moving": reproject_moving,
                "rectify": rectify, "despike": despike, "specular_guides": specular_guides, "occlusion": occlusion,
-               "preview": preview, "openpbr": openpbr}
+               "gather": gather, "preview": preview, "openpbr": openpbr}
     want = sys.argv[1:] or list(entries) + ["host"]
     dev = pt.Device(0)
     res = {name: fn(pt, dev) for name, fn in entries.items() if name in want}
