@@ -212,6 +212,12 @@ int       ptGetSceneExtendForm(pt_scene* scene, uint32_t* form);
  * BLAS depth, each capped at the reference's Stack[32]); the extend kernel keeps
  * 20 in LDS and spills the rest to a per-ray global buffer. */
 int       ptSceneStackNeeded(pt_scene* scene, uint32_t* entries);
+/* Whether the uploaded scene's box tests take the exact fast slab division
+ * (1: every TLAS and BLAS box coordinate is 0 or has magnitude in
+ * [2^-50, 2^40], checked at every ptUpdateScene; 0: a coordinate outside it, so
+ * every box test divides, or no packs yet).  Results are the same either way
+ * (DESIGN.md §2); tests read it to state which branch they ran. */
+int       ptSceneFastDivision(pt_scene* scene, uint32_t* enabled);
 /* BLAS child pairs the extend kernel keeps in LDS for the uploaded scene
  * (the top levels of its BLASes, laid out first in the device node array;
  * 0 = no cache: scenes whose stack entries need 32 bits, or no mesh). */
@@ -763,6 +769,20 @@ int ptEvalNumerics(pt_device* device, uint32_t op, uint32_t n, const uint32_t* a
  * wrap > 1, or a texture index >= the scene's texture count. */
 int ptSampleTextures(pt_device* device, pt_scene* scene, uint32_t n, const uint32_t* texture_index,
                      const float* uv, uint32_t wrap, float* rgba);
+
+/* Test probe: the traversal's slab test as the kernels call it, one case per
+ * thread.  Case i sets its level ray with SetLevelRay from origin[3 i ..] and
+ * velocity[3 i ..] under a scene of which only the box-coordinate gate
+ * (scene_gate, 0 or 1: dscene::fast_div) is set, then tests the box
+ * box_min[3 i ..], box_max[3 i ..] with IntersectBoxPair (the box as both
+ * children) against reach[i].  entry[i] receives the entry time's bit pattern
+ * (PT_INFINITY's for a miss), exact[i] the ray's fast-division flag (0 or 1).
+ * The host's counterpart is IEEE division: whenever the flag is set the entry
+ * time must equal it bit for bit (zeros of either sign aside).  Blocks.
+ * Fails, launching and writing nothing, on a NULL device, scene_gate > 1, or
+ * n > 0 with a NULL array; n == 0 succeeds. */
+int ptEvalSlabTest(pt_device* device, uint32_t n, const float* origin, const float* velocity, const float* reach,
+                   const float* box_min, const float* box_max, uint32_t scene_gate, uint32_t* entry, uint32_t* exact);
 
 /* Diagnostic: runs the extend step on the renderer's current rays with
  * traversal counters.  It writes the same hit records the next Run's extend

@@ -516,10 +516,12 @@ HIP_API = {
     "ptCheckFastReciprocal": (_i32, [_vp, C.POINTER(C.c_uint64)]),
     "ptEvalNumerics": (_i32, [_vp, _u32, _u32, _u32ptr, _u32ptr, _u32ptr, _u32ptr]),
     "ptSampleTextures": (_i32, [_vp, _vp, _u32, _u32ptr, _fptr, _u32, _fptr]),
+    "ptEvalSlabTest": (_i32, [_vp, _u32, _fptr, _fptr, _fptr, _fptr, _fptr, _u32, _u32ptr, _u32ptr]),
     "ptExtendStats": (_i32, [_vp, _vp, C.POINTER(C.c_uint64)]),
     "ptExtendStepCounts": (_i32, [_vp, _vp, _vp]),
     "ptSetProfilingPeriod": (_i32, [_vp, C.c_uint32]),
     "ptSceneStackNeeded": (_i32, [_vp, C.POINTER(C.c_uint32)]),
+    "ptSceneFastDivision": (_i32, [_vp, C.POINTER(C.c_uint32)]),
     "ptSceneNodeCache": (_i32, [_vp, C.POINTER(C.c_uint32)]),
     "ptSetProfiling": (_i32, [_vp, _i32]),
     "ptGetKernelStats": (_i32, [_vp, _i32, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),

@@ -320,8 +320,13 @@ hipError_t pt_launch_finalize(const ptd::dscene& S, uint32_t n, const float4* hi
                               float2* uv, hipStream_t st);
 uint32_t pt_extend_stack_cap();
 // Test probes (probe.hip): one numerics operation (include/pt_numerics.h) over
-// n operand words, and SampleTexture at n caller-given UVs with either wrap.
+// n operand words, SampleTexture at n caller-given UVs with either wrap, and
+// the traversal's slab test (SetLevelRay + IntersectBoxPair) on n rays and
+// boxes under a scene of which only fast_div is read.
 hipError_t pt_launch_numerics_probe(uint32_t op, uint32_t n, const uint32_t* a, const uint32_t* b, const uint32_t* c,
                                     uint32_t* out, hipStream_t st);
 hipError_t pt_launch_sample_textures(const ptd::dscene& S, uint32_t n, const uint32_t* index, const float2* uv,
                                      bool unit_wrap, float4* rgba, hipStream_t st);
+hipError_t pt_launch_slab_probe(const ptd::dscene& S, uint32_t n, const float* origin, const float* velocity,
+                                const float* reach, const float* box_min, const float* box_max, uint32_t* entry,
+                                uint32_t* exact, hipStream_t st);

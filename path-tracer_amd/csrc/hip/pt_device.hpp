@@ -132,8 +132,12 @@ PT_DEV pt3 UnpackUnitVector(uint32_t P)
 // about 2^-46 |a|, which is below the smallest denormal for |a| < 2^-102
 // (tests/test_gpu_numerics.py found such quotients one ulp off).
 // ptCheckFastDivision verifies the equality over >10^9 operand pairs on the
-// device, ptEvalNumerics at chosen ones.  (The slab test uses the same
-// correction without a per-quotient guard: FastQuot below.)
+// device, ptEvalNumerics at chosen ones.  Both check XDiv only, which no
+// kernel calls.  The slab test uses the same correction WITHOUT a
+// per-quotient guard (FastQuot below) inside a domain that two gates enforce;
+// that function and its gates are checked by ptEvalSlabTest (probe.hip), which
+// runs SetLevelRay and IntersectBoxPair over the case sets of
+// tests/slab_cases.py (tests/test_gpu_slab_domain.py).
 PT_DEV float RecipForDiv(float b)
 {
     float m = pt_abs(b);
@@ -194,7 +198,9 @@ PT_DEV bool FastRcpRange(float d)
 // checked once per scene on the host (dscene::fast_div), the ray condition
 // once per ray and traversal level (FastDivRay); rays outside it take IEEE
 // division.  No NaN reaches the fast path, so plain hardware min/max give the
-// same comparisons as fminf/fmaxf.
+// same comparisons as fminf/fmaxf.  Both bounds of both gates, the smallest
+// numerators (2^-73) and the largest quotients (2^100) are held against IEEE
+// division bit for bit by tests/test_gpu_slab_domain.py.
 PT_DEV bool FastDivRay(pt3 O, pt3 V)
 {
     bool ok = true;

@@ -1,6 +1,6 @@
 // rt_probe.hip — host side of libpathtracer.so: the test probes: ray queries, traversal
-// counters, device numerics and the texture sampler, each checked against the
-// host by the tests.
+// counters, device numerics, the texture sampler and the slab test, each
+// checked against the host by the tests.
 #include "runtime.hpp"
 #include "../../../include/pt_visibility.h"
 
@@ -292,6 +292,34 @@ int ptSampleTextures(pt_device* d, pt_scene* s, uint32_t n, const uint32_t* text
         e = hipMemcpy(rgba, d_rgba.ptr, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost);
     } while (0);
     if (e != hipSuccess) { SetError("ptSampleTextures: %s", hipGetErrorString(e)); return (int)e; }
+    return 0;
+}
+
+int ptEvalSlabTest(pt_device* d, uint32_t n, const float* origin, const float* velocity, const float* reach,
+                   const float* box_min, const float* box_max, uint32_t scene_gate, uint32_t* entry, uint32_t* exact)
+{
+    if (!d || (n && (!origin || !velocity || !reach || !box_min || !box_max || !entry || !exact))) {
+        SetError("null argument");
+        return -1;
+    }
+    if (scene_gate > 1) { SetError("ptEvalSlabTest: scene_gate %u", scene_gate); return -1; }
+    if (n == 0) return 0;
+    PT_HIP(hipSetDevice(d->id));
+    ptd::dscene S{};
+    S.fast_div = scene_gate;
+    dbuf<float> d_o, d_v, d_r, d_lo, d_hi;
+    dbuf<uint32_t> d_entry, d_exact;
+    PT_HIP(d_o.upload(origin, (size_t)n * 3));
+    PT_HIP(d_v.upload(velocity, (size_t)n * 3));
+    PT_HIP(d_r.upload(reach, n));
+    PT_HIP(d_lo.upload(box_min, (size_t)n * 3));
+    PT_HIP(d_hi.upload(box_max, (size_t)n * 3));
+    PT_HIP(d_entry.alloc(n));
+    PT_HIP(d_exact.alloc(n));
+    PT_HIP(pt_launch_slab_probe(S, n, d_o.ptr, d_v.ptr, d_r.ptr, d_lo.ptr, d_hi.ptr, d_entry.ptr, d_exact.ptr, d->stream));
+    PT_HIP(hipMemcpyAsync(entry, d_entry.ptr, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    PT_HIP(hipMemcpyAsync(exact, d_exact.ptr, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, d->stream));
+    PT_HIP(hipStreamSynchronize(d->stream));
     return 0;
 }
 

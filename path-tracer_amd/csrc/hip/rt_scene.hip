@@ -527,6 +527,13 @@ int ptSceneStackNeeded(pt_scene* s, uint32_t* entries)
     return 0;
 }
 
+int ptSceneFastDivision(pt_scene* s, uint32_t* enabled)
+{
+    if (!s || !enabled) { SetError("null argument"); return -1; }
+    *enabled = s->valid ? s->d.fast_div : 0u;
+    return 0;
+}
+
 int ptSceneNodeCache(pt_scene* s, uint32_t* pairs)
 {
     if (!s || !pairs) { SetError("null argument"); return -1; }

@@ -74,6 +74,22 @@ class Device(Handle):
         hip("ptEvalNumerics", self._h, N.NUMERICS_OPS.index(name), n, *ptrs, N.u32ptr(out))
         return out if outputs == 1 else out.reshape(n, outputs)
 
+    def eval_slab_test(self, origin, velocity, reach, box_min, box_max, scene_gate: int = 1):
+        """Test probe (ptEvalSlabTest): the traversal's slab test of n rays
+        ((n, 3) origins and velocities, (n,) reaches) against n boxes ((n, 3)
+        minima and maxima), the level ray set as the kernels set it under a
+        scene whose box-coordinate gate is `scene_gate`.  Returns (entry time
+        bit patterns, fast-division flags), each uint32 of shape (n,)."""
+        o, v, lo, hi = (np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3) for x in (origin, velocity, box_min, box_max))
+        r = np.ascontiguousarray(reach, dtype=np.float32).reshape(-1)
+        n = len(r)
+        if not (len(o) == len(v) == len(lo) == len(hi) == n):
+            raise ValueError("eval_slab_test: arrays of different lengths")
+        entry, exact = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        hip("ptEvalSlabTest", self._h, n, N.fptr(o), N.fptr(v), N.fptr(r), N.fptr(lo), N.fptr(hi), int(scene_gate),
+            N.u32ptr(entry), N.u32ptr(exact))
+        return entry, exact
+
 
 def _records(pointer, count: int, dtype: np.dtype) -> np.ndarray:
     """A copy of `count` packed records at `pointer` (none for a null pointer)."""
@@ -137,6 +153,12 @@ class DeviceScene(Handle):
     def stack_needed(self) -> int:
         """Traversal stack entries the uploaded scene can need (TLAS + BLAS depth)."""
         return hip_get("ptSceneStackNeeded", self._h)
+
+    @property
+    def fast_division(self) -> bool:
+        """Whether the uploaded scene's box tests take the exact fast slab
+        division (every box coordinate 0 or in [2^-50, 2^40]; ptSceneFastDivision)."""
+        return bool(hip_get("ptSceneFastDivision", self._h))
 
     @property
     def node_cache_pairs(self) -> int:

@@ -98,6 +98,9 @@ def test_null_arguments_rejected(pt):
     fp = uv.ctypes.data_as(C.POINTER(C.c_float))
     assert L.ptSampleTextures(None, None, 2, wp, fp, 0, fp) != 0
     assert b"null" in L.ptGetLastError()
+    assert L.ptEvalSlabTest(None, 1, fp, fp, fp, fp, fp, 1, wp, wp) != 0
+    assert b"null" in L.ptGetLastError()
+    assert L.ptSceneFastDivision(None, wp) != 0
     assert not words.any() and not uv.any()
 
 
