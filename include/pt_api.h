@@ -41,7 +41,8 @@
  * closest-hit query hits") with an ambient-occlusion / sky-visibility image
  * built on it (ptRenderAmbientOcclusion), and the same lobe gathered at
  * caller-given points: an occlusion count, mask and bent vector per point
- * (ptGatherVisibility).
+ * (ptGatherVisibility), and the sky's light that reaches such points as nine
+ * spherical-harmonic coefficients per CIE XYZ channel (ptGatherSkyLight).
  *
  * Conventions: creators return NULL on failure and set ptGetLastError();
  * other calls return 0 on success or a non-zero status (HIP / RCCL error
@@ -107,7 +108,7 @@ typedef struct pt_pixel_state {
 
 enum {
     PT_KERNEL_RAYGEN  = 0,
-    PT_KERNEL_EXTEND  = 1,   /* also ptTraceRays' extend launch, ptOccludedRays' launch and ptGatherVisibility's launches */
+    PT_KERNEL_EXTEND  = 1,   /* also ptTraceRays' extend launch, ptOccludedRays' launch, ptGatherVisibility's launches and ptGatherSkyLight's launches */
     PT_KERNEL_SHADE   = 2,
     PT_KERNEL_RESOLVE = 3,
     PT_KERNEL_PREVIEW = 4,
@@ -857,6 +858,51 @@ int ptGatherVisibility(pt_device* device, pt_scene* scene, uint32_t n, const flo
 int ptGatherVisibilityChunked(pt_device* device, pt_scene* scene, uint32_t n, const float* points,
                               const float* normals, const pt_visibility_gather_parameters* params,
                               uint32_t max_lanes, pt_visibility_record* out);
+
+/* Sky light gathered at caller-given points (no reference counterpart;
+ * definition in pt_visibility.h and DESIGN.md §6 row 16): every scene is lit by
+ * its sky alone, so the first-order lighting of a point is the sky's radiance
+ * over the directions that are not blocked.  points (and normals, with
+ * params->Lobe == PT_SKY_GATHER_COSINE) hold 3 floats per point and are used
+ * as given.  Point i draws params->Samples rays from the random stream
+ * params->FirstIndex + i of frame params->Seed: with Lobe COSINE exactly
+ * ptGatherVisibility's rays for the same Samples, Radius, Seed, Offset and
+ * FirstIndex; with Lobe SPHERE uniform over the sphere, and normals is not read
+ * (it may be NULL).  Each ray goes through ptOccludedRays' any-hit traversal,
+ * one lane per (point, sample); an open ray contributes what a camera ray
+ * leaving the scene along it adds to its pixel (the sky's radiance at four
+ * wavelengths of a draw of the same stream, observed to CIE XYZ, in the
+ * integrator's units), times the nine real spherical harmonics of bands 0..2
+ * along it (z up; pt_sky_gather_basis).  out[i] is the point's pt_sky_record
+ * (pt_packed.h): SH[i][c] summed by a fixed tree, so two calls give the same
+ * bits; OccludedMask, Unoccluded and Samples as ptGatherVisibility's, and with
+ * Lobe COSINE equal to them.
+ *
+ * Reading a record of S samples, Y0 = 0.28209479:
+ *   COSINE: pi * SH[0][c] / (Y0 * S) is the XYZ irradiance from the sky at the
+ *           point; SH[0][c] / (Y0 * S) is the pixel value the integrator
+ *           converges to for direct sky light on a white Lambertian surface
+ *           there.
+ *   SPHERE: (4 pi / S) * SH[i][c] are the SH9 coefficients of the visible
+ *           sky's radiance around the point (a light probe).
+ * Records of other Seeds add, field by field, to a record of more samples.
+ *
+ * Nesting and partition independence hold as for ptGatherVisibility.  Uploads
+ * 12 or 24 bytes per point, launches in chunks of whole points and at most
+ * 2^22 lanes (each launch counted under PT_KERNEL_EXTEND), reads back 128
+ * bytes per point and blocks.  n == 0 succeeds and touches nothing.  Fails,
+ * launching and writing nothing, on a NULL argument (the arrays with n > 0;
+ * normals only with Lobe COSINE), a scene of another device or without packs,
+ * a Lobe other than the two, or Samples, Radius, Offset, n or FirstIndex
+ * outside ptGatherVisibility's ranges. */
+int ptGatherSkyLight(pt_device* device, pt_scene* scene, uint32_t n, const float* points, const float* normals,
+                     const pt_sky_gather_parameters* params, pt_sky_record* out);
+/* Test probe: ptGatherSkyLight with launches of at most max_lanes lanes
+ * (64..2^22; ptGatherSkyLight passes 2^22).  The records do not depend on
+ * max_lanes. */
+int ptGatherSkyLightChunked(pt_device* device, pt_scene* scene, uint32_t n, const float* points,
+                            const float* normals, const pt_sky_gather_parameters* params, uint32_t max_lanes,
+                            pt_sky_record* out);
 
 /* Per-kernel device time, measured with HIP events on the renderer stream. */
 int ptSetProfiling(pt_device* device, int enable);

@@ -287,6 +287,34 @@ typedef struct pt_visibility_record {
     uint32_t Reserved;                 /* 0 */
 } pt_visibility_record;
 
+/* Sky light gathered at caller-given points (arithmetic
+ * in pt_visibility.h): row 15's rays, or rays uniform over the sphere, each
+ * open one weighted by the sky's radiance along it. */
+#define PT_SKY_GATHER_COSINE 0u        /* row 15's cosine lobe around the point's normal */
+#define PT_SKY_GATHER_SPHERE 1u        /* uniform over the sphere; the normal is not read */
+
+typedef struct pt_sky_gather_parameters {
+    uint32_t Samples;                  /* 1, 2, 4, 8, 16, 32 or 64, default 16: rays per point */
+    float    Radius;                   /* > 0, default +inf; at or beyond PT_HIT_TIME_LIMIT (+inf): every occluder counts */
+    uint32_t Seed;                     /* default 0: the integrator's FrameIndex of the streams the rays are drawn from */
+    float    Offset;                   /* finite, >= 0, default 1e-3: a ray starts at P + Offset * W */
+    uint32_t FirstIndex;               /* default 0: point i draws from stream FirstIndex + i; FirstIndex + n <= 2^32 */
+    uint32_t Lobe;                     /* PT_SKY_GATHER_COSINE (default) or PT_SKY_GATHER_SPHERE */
+} pt_sky_gather_parameters;
+
+/* One point's answer.  SH[i][c]: the sum over the point's rays of (the open
+ * ray's escape contribution in CIE XYZ channel c) * (real spherical harmonic i
+ * of bands 0..2 along the ray, pt_sky_gather_basis), by the fixed pairwise
+ * tree of pt_sky_gather_reduce.  OccludedMask, Unoccluded, Samples: as in
+ * pt_visibility_record. */
+typedef struct pt_sky_record {
+    float    SH[9][3];
+    float    Unoccluded;               /* Samples - popcount(OccludedMask) */
+    uint64_t OccludedMask;             /* at byte 112 */
+    float    Samples;
+    uint32_t Reserved[1];              /* 0 */
+} pt_sky_record;
+
 /* One shape's motion between two packed scenes, filled
  * by ptsShapeMotion (pt_scene.h) and read by the moving-shape reprojection
  * (pt_reproject.h).  Point: rows 0..2 of the affine map from the current
@@ -355,6 +383,8 @@ static_assert(sizeof(pt_despike_parameters) == 24, "despike_parameters");
 static_assert(sizeof(pt_ambient_occlusion_parameters) == 12, "ambient_occlusion_parameters");
 static_assert(sizeof(pt_visibility_gather_parameters) == 20, "visibility_gather_parameters");
 static_assert(sizeof(pt_visibility_record) == 32, "visibility_record");
+static_assert(sizeof(pt_sky_gather_parameters) == 24, "sky_gather_parameters");
+static_assert(sizeof(pt_sky_record) == 128, "sky_record");
 static_assert(sizeof(pt_shape_motion) == 96, "shape_motion");
 static_assert(sizeof(pt_packed_transform) == 128, "packed_transform");
 static_assert(sizeof(pt_packed_texture) == 32, "packed_texture");

@@ -298,6 +298,25 @@ int  ptsGatherVisibilityReduce(uint32_t samples, uint32_t n, const uint32_t* pac
 /* pt_visibility_skip as a library call: `state` after `steps` steps of the
  * random stream's generator. */
 uint32_t ptsVisibilitySkip(uint32_t state, uint32_t steps);
+/* The rays of ptGatherSkyLight (pt_api.h) on the host, bit
+ * for bit, point-major, for both lobes: as ptsGatherVisibilityRays, and
+ * out_lambda0 receives each ray's normalised first wavelength L0 (the path's
+ * four wavelengths are PathLambda(L0)).  normals may be NULL with Lobe SPHERE.
+ * Non-zero, writing nothing, on a NULL argument (the arrays with n > 0) or
+ * parameters outside their range. */
+int  ptsSkyGatherRays(const pt_sky_gather_parameters* params, uint32_t n, const float* points, const float* normals,
+                      float* out_origins, uint32_t* out_velocities, float* out_durations, float* out_lambda0);
+/* ptGatherSkyLight's records from a one-bit-per-ray answer over those rays
+ * (ptOccludedRays' mask layout) and any per-ray XYZ contributions (3 floats
+ * per ray; an occluded ray's is taken as zero): the basis, the products and
+ * the device's summation tree.  The sky evaluation is not part of this
+ * library.  Non-zero, writing nothing, on samples not a power of two in
+ * 1..64, n > 2^26 or a NULL array with n > 0. */
+int  ptsSkyGatherReduce(uint32_t samples, uint32_t n, const uint32_t* packed, const uint64_t* occluded_bits,
+                        const float* contributions, pt_sky_record* out);
+/* pt_sky_gather_basis as a library call: 9 floats per packed unit vector, at
+ * the unpacked vector. */
+int  ptsSkyGatherBasis(uint32_t n, const uint32_t* packed, float* out);
 
 /* Frame statistics on the host (no reference counterpart; definition in
  * DESIGN.md §6 row 6, arithmetic in pt_stats.h): the CPU path for saved

@@ -226,4 +226,114 @@ PT_HD pt_visibility_record pt_visibility_reduce(uint32_t S, const uint32_t* pack
     return R;
 }
 
+/* --- sky light gathered at caller-given points -----------
+ *
+ * The device kernel is sky_gather_kernel (csrc/hip/occlusion.hip), the host
+ * twins ptsSkyGatherRays / ptsSkyGatherReduce (csrc/scene/visibility.cpp),
+ * the numpy restatement tests/sky_gather_restatement.py.
+ *
+ * Point i of n, position P and (COSINE only) normal N as given, parameters
+ * {Samples S, Radius, Seed, Offset, FirstIndex, Lobe}:
+ *
+ *   j  = FirstIndex + i;  s0 = pt_visibility_gather_seed(j, Seed)
+ *   sample k = 0 .. S-1:
+ *     state = pt_visibility_skip(s0, 2 k); D = RandomDirection(state)
+ *     COSINE: W as row 15's (ray k is row 15's ray k, bit for bit)
+ *     SPHERE: W = D, uniform over the sphere; N is not read
+ *     word = pack(W), V = unpack(word); origin P + Offset W; duration
+ *            pt_visibility_duration(Radius)
+ *     lstate = pt_visibility_skip(s0, 128 + k)   (past the 128 direction draws
+ *            of the largest S); L0 = Random0To1(lstate); Lambda = PathLambda(L0)
+ *     occ_k = whether anything lies within ray k's duration
+ *     C_k = occ_k ? (0, 0, 0) : EscapeContribution(scene, V, Lambda, (1, 1, 1, 1), 4)
+ *            (csrc/hip/path.hpp: what a camera ray leaving the scene along V
+ *            adds to its pixel, CIE XYZ)
+ *     Y[0..8] = pt_sky_gather_basis(V);  t[i][c] = C_k[c] * Y[i]
+ *   record (pt_sky_record): SH[i][c] = the pairwise tree sum of t[i][c] over k
+ *     (b'_m = b_2m + b_2m+1 for log2 S levels, row 15's tree per float);
+ *     OccludedMask, Unoccluded, Samples as row 15's; Reserved = 0.
+ *
+ * The sky evaluation itself is the device's (and the restatement's): this
+ * header has the rays, L0, the basis and the tree.  Nesting and partition
+ * independence hold as in row 15. */
+
+/* pt_visibility_gather_parameters_ok's ranges, and a known Lobe. */
+PT_HD int pt_sky_gather_parameters_ok(const pt_sky_gather_parameters* p, uint32_t n)
+{
+    pt_visibility_gather_parameters q;
+    q.Samples = p->Samples;
+    q.Radius = p->Radius;
+    q.Seed = p->Seed;
+    q.Offset = p->Offset;
+    q.FirstIndex = p->FirstIndex;
+    if (p->Lobe != PT_SKY_GATHER_COSINE && p->Lobe != PT_SKY_GATHER_SPHERE) return 0;
+    return pt_visibility_gather_parameters_ok(&q, n);
+}
+
+/* Sample k of the point at P whose stream starts at s0: its origin, and its
+ * velocity as the packed word.  COSINE: pt_visibility_gather_ray around N.
+ * SPHERE: the drawn direction itself; N is not used. */
+PT_HD uint32_t pt_sky_gather_ray(uint32_t Lobe, pt3 N, pt3 P, float Offset, uint32_t s0, uint32_t k, pt3* RO)
+{
+    if (Lobe == PT_SKY_GATHER_COSINE) {
+        const pt_visibility_frame F = pt_visibility_gather_frame(N);
+        return pt_visibility_gather_ray(&F, P, Offset, s0, k, RO);
+    }
+    uint32_t state = pt_visibility_skip(s0, 2u * k);
+    const pt3 W = pt_visibility_random_direction(&state);
+    *RO = P + Offset * W;
+    return pt_reproject_pack_unit(W);
+}
+
+/* Sample k's normalised first wavelength: draw 128 + k of the point's stream. */
+PT_HD float pt_sky_gather_lambda0(uint32_t s0, uint32_t k)
+{
+    uint32_t lstate = pt_visibility_skip(s0, 128u + k);
+    return pt_random01(&lstate);
+}
+
+/* The real spherical harmonics of bands 0..2 at the unit vector V, z up. */
+PT_HD void pt_sky_gather_basis(pt3 V, float Y[9])
+{
+    const float x = V.x, y = V.y, z = V.z;
+    Y[0] = 0.28209479f;
+    Y[1] = 0.48860251f * y;
+    Y[2] = 0.48860251f * z;
+    Y[3] = 0.48860251f * x;
+    Y[4] = 1.09254843f * (x * y);
+    Y[5] = 1.09254843f * (y * z);
+    Y[6] = 0.31539157f * (3.0f * (z * z) - 1.0f);
+    Y[7] = 1.09254843f * (x * z);
+    Y[8] = 0.54627422f * (x * x - y * y);
+}
+
+/* A point's record from its S packed velocities, its occluded bits and its
+ * rays' contributions (3 floats per ray; an occluded ray's is taken as zero):
+ * the basis, the 27 products per ray and the tree the device kernel's
+ * cross-lane rounds form. */
+PT_HD pt_sky_record pt_sky_gather_reduce(uint32_t S, const uint32_t* packed, uint64_t occluded, const float* contributions)
+{
+    float b[PT_AMBIENT_OCCLUSION_MAX_SAMPLES][27];
+    uint32_t count = 0u;
+    for (uint32_t k = 0; k < S; k++) {
+        const int occ = (int)((occluded >> k) & 1u);
+        count += (uint32_t)occ;
+        float Y[9];
+        pt_sky_gather_basis(pt_reproject_unpack_unit(packed[k]), Y);
+        for (uint32_t i = 0; i < 9u; i++)
+            for (uint32_t c = 0; c < 3u; c++) b[k][3u * i + c] = (occ ? 0.0f : contributions[3u * k + c]) * Y[i];
+    }
+    for (uint32_t w = S; w > 1u; w >>= 1u)
+        for (uint32_t m = 0; m < w / 2u; m++)
+            for (uint32_t e = 0; e < 27u; e++) b[m][e] = b[2u * m][e] + b[2u * m + 1u][e];
+    pt_sky_record R;
+    for (uint32_t i = 0; i < 9u; i++)
+        for (uint32_t c = 0; c < 3u; c++) R.SH[i][c] = b[0][3u * i + c];
+    R.Unoccluded = (float)(S - count);
+    R.OccludedMask = S < 64u ? occluded & ((1ull << S) - 1ull) : occluded;
+    R.Samples = (float)S;
+    R.Reserved[0] = 0u;
+    return R;
+}
+
 #endif /* PT_VISIBILITY_H */

@@ -21,7 +21,9 @@ from .integrator import (Device, DeviceScene, SampleBuffer, BasicRenderer, Comm,
                          reproject_host, FrameHistory, shape_motion, tile_statistics_host, tile_mask_of_region,
                          refine_tiles, REFINE_MIN_ROUNDS, RectifyParameters, rectify_host, DespikeParameters,
                          despike_host, AmbientOcclusionParameters, VisibilityGatherParameters,
-                         gather_visibility_rays_host, gather_visibility_reduce_host, shape_surface_points)
+                         gather_visibility_rays_host, gather_visibility_reduce_host, shape_surface_points, SkyGatherParameters,
+                         sky_gather_rays_host, sky_gather_reduce_host, sh9_basis, sky_irradiance, sky_radiance_sh,
+                         sh9_irradiance)
 from ._native import (PREVIEW_RENDER_MODE_BASE_COLOR, PREVIEW_RENDER_MODE_BASE_COLOR_SHADED, PREVIEW_RENDER_MODE_NORMAL,
                       PREVIEW_RENDER_MODE_MATERIAL_INDEX, PREVIEW_RENDER_MODE_PRIMITIVE_INDEX,
                       PREVIEW_RENDER_MODE_MESH_COMPLEXITY, PREVIEW_RENDER_MODE_SCENE_COMPLEXITY)
@@ -36,6 +38,7 @@ from ._native import SHAPE_DTYPE, SHAPE_MOTION_DTYPE, SHAPE_MOTION_MOVED, SHAPE_
 from ._native import AMBIENT_OCCLUSION_MAX_SAMPLES
 from ._native import VISIBILITY_RECORD_DTYPE, VISIBILITY_GATHER_MAX_POINTS
 from .image import write_png, write_ppm, write_pfm, read_png
-from .layout import band_rows, owned_pixels
+from ._native import SKY_GATHER_COSINE, SKY_GATHER_SPHERE
+from .layout import band_rows, owned_pixels, SKY_RECORD_DTYPE
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -176,6 +176,23 @@ assert VISIBILITY_RECORD_DTYPE.itemsize == 32
 VISIBILITY_GATHER_MAX_POINTS = 1 << 26   # PT_VISIBILITY_GATHER_MAX_POINTS (include/pt_visibility.h)
 VISIBILITY_GATHER_MAX_LANES = 1 << 22    # PT_VISIBILITY_GATHER_MAX_LANES
 
+
+class pt_sky_gather_parameters(C.Structure):
+    """pt_sky_gather_parameters (include/pt_packed.h)."""
+    _fields_ = [
+        ("Samples", C.c_uint32),
+        ("Radius", C.c_float),
+        ("Seed", C.c_uint32),
+        ("Offset", C.c_float),
+        ("FirstIndex", C.c_uint32),
+        ("Lobe", C.c_uint32),
+    ]
+
+
+assert C.sizeof(pt_sky_gather_parameters) == 24
+SKY_GATHER_COSINE = 0   # PT_SKY_GATHER_COSINE (include/pt_packed.h)
+SKY_GATHER_SPHERE = 1   # PT_SKY_GATHER_SPHERE
+
 STATS_BINS = 256
 
 
@@ -404,6 +421,9 @@ SCENE_API = {
                                        _fptr]),
     "ptsGatherVisibilityReduce": (_i32, [_u32, _u32, _u32ptr, C.POINTER(C.c_uint64), _vp]),
     "ptsVisibilitySkip": (_u32, [_u32, _u32]),
+    "ptsSkyGatherRays": (_i32, [C.POINTER(pt_sky_gather_parameters), _u32, _fptr, _fptr, _fptr, _u32ptr, _fptr, _fptr]),
+    "ptsSkyGatherReduce": (_i32, [_u32, _u32, _u32ptr, C.POINTER(C.c_uint64), _fptr, _vp]),
+    "ptsSkyGatherBasis": (_i32, [_u32, _u32ptr, _fptr]),
     "ptsFrameStatistics": (_i32, [_u32, _u32, _fptr, _fptr, C.POINTER(pt_frame_statistics)]),
     "ptsTileStatistics": (_i32, [_u32, _u32, _fptr, _fptr, _f32, _vp]),
     "ptsStatsBin": (_i32, [C.c_float]),
@@ -484,6 +504,8 @@ HIP_API = {
     "ptGatherVisibility": (_i32, [_vp, _vp, _u32, _fptr, _fptr, C.POINTER(pt_visibility_gather_parameters), _vp]),
     "ptGatherVisibilityChunked": (_i32, [_vp, _vp, _u32, _fptr, _fptr, C.POINTER(pt_visibility_gather_parameters),
                                          _u32, _vp]),
+    "ptGatherSkyLight": (_i32, [_vp, _vp, _u32, _fptr, _fptr, C.POINTER(pt_sky_gather_parameters), _vp]),
+    "ptGatherSkyLightChunked": (_i32, [_vp, _vp, _u32, _fptr, _fptr, C.POINTER(pt_sky_gather_parameters), _u32, _vp]),
     "ptCreatePreviewRenderContext": (_vp, [_vp, _vp]),
     "ptDestroyPreviewRenderContext": (None, [_vp, _vp]),
     "ptRenderPreview": (_i32, [_vp, _vp, C.POINTER(pt_preview_parameters)]),

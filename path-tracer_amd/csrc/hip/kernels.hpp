@@ -316,6 +316,14 @@ hipError_t pt_launch_ambient_occlusion(const ptd::dscene& S, uint32_t camera_ind
 hipError_t pt_launch_gather_visibility(const ptd::dscene& S, uint32_t n, const float* points, const float* normals,
                                        const pt_visibility_gather_parameters* p, uint32_t first_index, uint32_t* spill,
                                        float4* out, hipStream_t st);
+// Sky light gathered at n points (occlusion.hip; include/pt_visibility.h; DESIGN.md
+// §6 row 16): one lane per (point, sample), n * Samples <= 2^22 lanes -> out,
+// eight float4 per point (pt_sky_record).  normals may be null with Lobe SPHERE.
+// The other arguments as pt_launch_gather_visibility's.  p has passed
+// pt_sky_gather_parameters_ok.
+hipError_t pt_launch_gather_sky_light(const ptd::dscene& S, uint32_t n, const float* points, const float* normals,
+                                      const pt_sky_gather_parameters* p, uint32_t first_index, uint32_t* spill,
+                                      float4* out, hipStream_t st);
 hipError_t pt_launch_finalize(const ptd::dscene& S, uint32_t n, const float4* hit, const float2* hc, float4* rec,
                               float2* uv, hipStream_t st);
 uint32_t pt_extend_stack_cap();

@@ -1,7 +1,8 @@
 // occlusion.hip — the any-hit query (no reference counterpart; DESIGN.md §6
 // row 14): whether anything lies within a ray's duration, one bit per ray, and
 // the ambient-occlusion / sky-visibility image built on it, and the same lobe
-// gathered at caller-given points (row 15); with their launchers.
+// gathered at caller-given points (row 15), and the sky's light gathered at
+// such points as spherical harmonics (row 16); with their launchers.
 //
 // The any-hit traversal is Trace() stopped at the first step that leaves an
 // accepted intersection in the lane (Hit.ShapeIndex set).  Until that step
@@ -298,6 +299,100 @@ __global__ __launch_bounds__(256, 8) void visibility_gather_kernel(dscene S, gat
     }
 }
 
+// --- sky light gathered at caller-given points ----------------
+
+struct sky_gather_args {
+    const float* points;    // 3 floats per point
+    const float* normals;   // 3 floats per point; not read (may be null) with lobe SPHERE
+    uint32_t n;             // points of this launch; n << shift lanes are live
+    uint32_t shift;         // log2 of the samples per point
+    uint32_t seed;
+    uint32_t first;         // stream index of point 0
+    float offset;
+    float duration;
+    uint32_t lobe;          // PT_SKY_GATHER_COSINE / PT_SKY_GATHER_SPHERE
+};
+
+// visibility_gather_kernel's shape: a lane per (point, sample), a point an
+// aligned segment of one wave, every lane at the node-cache fill's barrier,
+// the ballot and the shuffles.  After the trace the open lanes alone look the
+// sky up along their ray (texture sample, four parametric spectra, four
+// observer values: EscapeContribution of a fresh path); occluded and dead lanes
+// hold a zero contribution, and every lane forms the 27 products with its
+// basis, so a zero carries the sign the definition gives it.  The 27 sums
+// take log2 S rounds of __shfl_xor within the segment, after which every lane
+// of the segment holds the whole record as 8 float4: lane k < 8 stores the
+// float4s j with j % S == k (with S >= 8, one each), constant register indices
+// under a predicate, so nothing is indexed dynamically.
+template <bool SPILL, int CAP, class E, bool NC, bool MESH>
+__global__ __launch_bounds__(256, 8) void sky_gather_kernel(dscene S, sky_gather_args P, uint32_t* spill,
+                                                            uint32_t spill_stride, float4* __restrict__ out)
+{
+    __shared__ E smem[CAP * 256];
+    __shared__ float4 ncache[NC ? 4 * PT_NODE_CACHE_PAIRS : 1];
+    const uint32_t ncn = NC ? NodeCacheFill(S, ncache) : 0u;
+    const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+    const uint32_t samples = 1u << P.shift;
+    const uint32_t point = g >> P.shift, k = g & (samples - 1u);
+    const bool live = point < P.n;
+    bool occluded = false;
+    uint32_t word = 0;
+    if (live) {
+        tstack<SPILL, CAP, E> st;
+        st.lds = &smem[threadIdx.x];
+        st.spill = spill + g;
+        st.stride = spill_stride;
+        st.nc = ncache;
+        st.ncn = ncn;
+        const float* p = P.points + 3 * (size_t)point;
+        pt3 Nrm = v3(0, 0, 0);
+        if (P.lobe == PT_SKY_GATHER_COSINE) {
+            const float* nrm = P.normals + 3 * (size_t)point;
+            Nrm = v3(nrm[0], nrm[1], nrm[2]);
+        }
+        pt3 RO;
+        word = pt_sky_gather_ray(P.lobe, Nrm, v3(p[0], p[1], p[2]), P.offset,
+                                 pt_visibility_gather_seed(P.first + point, P.seed), k, &RO);
+        const ray_source_held cur{RO, pt_reproject_unpack_unit(word)};
+        no_stats ns;
+        occluded = AnyHit<SPILL, CAP, E, MESH>(S, st, cur, g, cur.O, cur.V, P.duration, ns);
+    }
+    const unsigned long long ballot = __ballot(occluded);
+    const pt3 V = pt_reproject_unpack_unit(word);
+    pt3 Ck = v3(0, 0, 0);
+    if (live && !occluded) {
+        const float L0 = pt_sky_gather_lambda0(pt_visibility_gather_seed(P.first + point, P.seed), k);
+        Ck = EscapeContribution(S, V, PathLambda(L0), v4s(1.0f), 4.0f);
+    }
+    float Y[9];
+    pt_sky_gather_basis(V, Y);
+    float r[32];
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        r[3 * i] = Ck.x * Y[i];
+        r[3 * i + 1] = Ck.y * Y[i];
+        r[3 * i + 2] = Ck.z * Y[i];
+    }
+    for (uint32_t o = 1; o < samples; o <<= 1) {
+#pragma unroll
+        for (int e = 0; e < 27; e++) r[e] = r[e] + __shfl_xor(r[e], (int)o, 64);
+    }
+    const unsigned long long segment = ballot >> (threadIdx.x & 63u & ~(samples - 1u));
+    const unsigned long long mask = P.shift == 6u ? segment : segment & ((1ull << samples) - 1ull);
+    const float Sf = (float)samples;
+    r[27] = Sf - (float)__popcll(mask);
+    r[28] = __uint_as_float((uint32_t)mask);
+    r[29] = __uint_as_float((uint32_t)(mask >> 32));
+    r[30] = Sf;
+    r[31] = __uint_as_float(0u);
+    if (live && k < 8u) {
+        float4* const rec = out + 8 * (size_t)point;
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; j++)
+            if ((j & (samples - 1u)) == k) rec[j] = make_float4(r[4 * j], r[4 * j + 1], r[4 * j + 2], r[4 * j + 3]);
+    }
+}
+
 }  // namespace ptd
 
 // --- launchers (called from rt_probe.hip and rt_post.hip) --------------------------
@@ -350,6 +445,38 @@ hipError_t pt_launch_gather_visibility(const ptd::dscene& S, uint32_t n, const f
             [&](auto SPILL, auto NC, auto MESH) {
                 if constexpr (!NC || ptv::HasOcclusionNodeCache<E>(SPILL))
                     hipLaunchKernelGGL((ptd::visibility_gather_kernel<SPILL, PT_EXTEND_CAP, E, NC, MESH>),
+                                       dim3(Blocks(lanes)), dim3(256), 0, st, S, P, spill, lanes, out);
+            },
+            spill != nullptr, cache, S.single_mesh != 0);
+    });
+    return hipGetLastError();
+}
+
+// sky_gather_kernel's instantiation is occlusion_kernel's, chosen the same way.
+hipError_t pt_launch_gather_sky_light(const ptd::dscene& S, uint32_t n, const float* points, const float* normals,
+                                      const pt_sky_gather_parameters* p, uint32_t first_index, uint32_t* spill,
+                                      float4* out, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    ptd::sky_gather_args P;
+    P.points = points;
+    P.normals = normals;
+    P.n = n;
+    P.shift = 0;
+    while ((1u << P.shift) < p->Samples) P.shift++;
+    P.seed = p->Seed;
+    P.first = first_index;
+    P.offset = p->Offset;
+    P.duration = pt_visibility_duration(p->Radius);
+    P.lobe = p->Lobe;
+    const uint32_t lanes = n << P.shift;
+    ptv::SelectStackEntry(S.stack16 != 0, [&](auto entry) {
+        using E = typename decltype(entry)::type;
+        const bool cache = S.node_cache && ptv::HasOcclusionNodeCache<E>(spill != nullptr);
+        ptv::SelectFlags(
+            [&](auto SPILL, auto NC, auto MESH) {
+                if constexpr (!NC || ptv::HasOcclusionNodeCache<E>(SPILL))
+                    hipLaunchKernelGGL((ptd::sky_gather_kernel<SPILL, PT_EXTEND_CAP, E, NC, MESH>),
                                        dim3(Blocks(lanes)), dim3(256), 0, st, S, P, spill, lanes, out);
             },
             spill != nullptr, cache, S.single_mesh != 0);

@@ -202,6 +202,57 @@ int ptGatherVisibility(pt_device* d, pt_scene* s, uint32_t n, const float* point
     return ptGatherVisibilityChunked(d, s, n, points, normals, params, PT_VISIBILITY_GATHER_MAX_LANES, out);
 }
 
+// Sky light gathered at caller-given points (occlusion.hip; DESIGN.md §6 row
+// 16): ptGatherVisibilityChunked's upload, whole-point chunks and spill rows;
+// eight float4 per point come back.  The normals are uploaded with Lobe COSINE
+// only.
+int ptGatherSkyLightChunked(pt_device* d, pt_scene* s, uint32_t n, const float* points, const float* normals,
+                            const pt_sky_gather_parameters* params, uint32_t max_lanes, pt_sky_record* out)
+{
+    if (!d || !s || !params || (n && (!points || !out))) { SetError("null argument"); return -1; }
+    if (s->dev != d) { SetError("ptGatherSkyLight: scene of another device"); return -1; }
+    if (!s->valid) { SetError("scene has no valid packs"); return -1; }
+    if (!pt_sky_gather_parameters_ok(params, n)) {
+        SetError("ptGatherSkyLight: Samples %u (a power of two up to 64), Radius %g (> 0), Offset %g (finite, >= 0), "
+                 "FirstIndex %u + n %u (n <= 2^26, the sum <= 2^32), Lobe %u (0 or 1)",
+                 params->Samples, (double)params->Radius, (double)params->Offset, params->FirstIndex, n, params->Lobe);
+        return -1;
+    }
+    const bool cosine = params->Lobe == PT_SKY_GATHER_COSINE;
+    if (n && cosine && !normals) { SetError("null argument"); return -1; }
+    if (max_lanes < PT_AMBIENT_OCCLUSION_MAX_SAMPLES || max_lanes > PT_VISIBILITY_GATHER_MAX_LANES) {
+        SetError("ptGatherSkyLightChunked: max_lanes %u outside 64..2^22", max_lanes);
+        return -1;
+    }
+    if (n == 0) return 0;
+    PT_HIP(hipSetDevice(d->id));
+    const uint32_t chunk = std::min(n, max_lanes / params->Samples);   // points per launch, >= 1
+    const bool spill = s->stack_needed > pt_extend_stack_cap();
+    dbuf<float> d_p, d_n;
+    dbuf<uint32_t> d_spill;
+    dbuf<float4> d_out;
+    PT_HIP(d_p.upload(points, (size_t)n * 3));
+    if (cosine) PT_HIP(d_n.upload(normals, (size_t)n * 3));
+    PT_HIP(d_out.alloc((size_t)n * 8));
+    if (spill) PT_HIP(d_spill.alloc((size_t)(s->stack_needed - pt_extend_stack_cap()) * chunk * params->Samples));
+    for (uint32_t a = 0; a < n; a += chunk) {
+        const uint32_t m = std::min(chunk, n - a);
+        PT_TIMED(d, PT_KERNEL_EXTEND,
+                 pt_launch_gather_sky_light(s->d, m, d_p.ptr + (size_t)a * 3, cosine ? d_n.ptr + (size_t)a * 3 : nullptr,
+                                            params, params->FirstIndex + a, spill ? d_spill.ptr : nullptr,
+                                            d_out.ptr + (size_t)a * 8, d->stream));
+    }
+    PT_HIP(hipMemcpyAsync(out, d_out.ptr, (size_t)n * sizeof(pt_sky_record), hipMemcpyDeviceToHost, d->stream));
+    PT_HIP(hipStreamSynchronize(d->stream));
+    return 0;
+}
+
+int ptGatherSkyLight(pt_device* d, pt_scene* s, uint32_t n, const float* points, const float* normals,
+                     const pt_sky_gather_parameters* params, pt_sky_record* out)
+{
+    return ptGatherSkyLightChunked(d, s, n, points, normals, params, PT_VISIBILITY_GATHER_MAX_LANES, out);
+}
+
 int ptCheckFastDivision(pt_device* d, uint64_t n, uint32_t seed, uint64_t* mismatches)
 {
     if (!d || !mismatches) { SetError("null argument"); return -1; }

@@ -67,3 +67,56 @@ extern "C" int ptsGatherVisibilityReduce(uint32_t samples, uint32_t n, const uin
 }
 
 extern "C" uint32_t ptsVisibilitySkip(uint32_t state, uint32_t steps) { return pt_visibility_skip(state, steps); }
+
+// The sky light gathered at points of DESIGN.md §6 row 16 on the host, from the
+// same header: the rays and first wavelengths sky_gather_kernel uses, and the
+// records from any one-bit-per-ray answer and per-ray contributions.  The sky
+// evaluation itself is the device's: this library has no texture sampler.
+
+extern "C" int ptsSkyGatherRays(const pt_sky_gather_parameters* params, uint32_t n, const float* points,
+                                const float* normals, float* out_origins, uint32_t* out_velocities,
+                                float* out_durations, float* out_lambda0)
+{
+    if (!params || (n && (!points || !out_origins || !out_velocities || !out_durations || !out_lambda0))) return -1;
+    if (!pt_sky_gather_parameters_ok(params, n)) return -1;
+    const bool cosine = params->Lobe == PT_SKY_GATHER_COSINE;
+    if (n && cosine && !normals) return -1;
+    const uint32_t S = params->Samples;
+    const float duration = pt_visibility_duration(params->Radius);
+    for (uint32_t i = 0; i < n; i++) {
+        const pt3 P = v3(points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2]);
+        const pt3 N = cosine ? v3(normals[3 * (size_t)i], normals[3 * (size_t)i + 1], normals[3 * (size_t)i + 2])
+                             : v3(0, 0, 0);
+        const uint32_t s0 = pt_visibility_gather_seed(params->FirstIndex + i, params->Seed);
+        for (uint32_t k = 0; k < S; k++) {
+            const size_t ray = (size_t)i * S + k;
+            pt3 RO;
+            out_velocities[ray] = pt_sky_gather_ray(params->Lobe, N, P, params->Offset, s0, k, &RO);
+            out_origins[3 * ray] = RO.x; out_origins[3 * ray + 1] = RO.y; out_origins[3 * ray + 2] = RO.z;
+            out_durations[ray] = duration;
+            out_lambda0[ray] = pt_sky_gather_lambda0(s0, k);
+        }
+    }
+    return 0;
+}
+
+extern "C" int ptsSkyGatherReduce(uint32_t samples, uint32_t n, const uint32_t* packed, const uint64_t* occluded_bits,
+                                  const float* contributions, pt_sky_record* out)
+{
+    if (samples < 1u || samples > PT_AMBIENT_OCCLUSION_MAX_SAMPLES || (samples & (samples - 1u)) != 0u) return -1;
+    if (n > PT_VISIBILITY_GATHER_MAX_POINTS || (n && (!packed || !occluded_bits || !contributions || !out))) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        // Ray i S + k is bit (i S + k) % 64 of word (i S + k) / 64; S divides 64.
+        const size_t ray = (size_t)i * samples;
+        out[i] = pt_sky_gather_reduce(samples, packed + ray, occluded_bits[ray >> 6] >> (ray & 63u),
+                                      contributions + 3 * ray);
+    }
+    return 0;
+}
+
+extern "C" int ptsSkyGatherBasis(uint32_t n, const uint32_t* packed, float* out)
+{
+    if (n && (!packed || !out)) return -1;
+    for (uint32_t i = 0; i < n; i++) pt_sky_gather_basis(pt_reproject_unpack_unit(packed[i]), out + 9 * (size_t)i);
+    return 0;
+}

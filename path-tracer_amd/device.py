@@ -9,7 +9,8 @@ import numpy as np
 
 from . import _native as N
 from ._core import U32, U64, F64, Handle, extend_stats, hip, hip_get
-from .params import VisibilityGatherParameters
+from .layout import SKY_RECORD_DTYPE
+from .params import SkyGatherParameters, VisibilityGatherParameters
 
 if TYPE_CHECKING:
     from .frame import SampleBuffer
@@ -215,6 +216,33 @@ class DeviceScene(Handle):
         out = np.zeros(len(p), dtype=N.VISIBILITY_RECORD_DTYPE)
         hip("ptGatherVisibility", self.device.handle, self._h, len(p), N.fptr(p), N.fptr(nrm), C.byref(s),
             out.ctypes.data)
+        return out
+
+    def gather_sky_light(self, points: np.ndarray, normals: "np.ndarray | None" = None, samples: int = 16,
+                         radius: float = float("inf"), seed: int = 0, offset: float = 1e-3, first_index: int = 0,
+                         lobe: "int | str" = "cosine", params: "SkyGatherParameters | None" = None) -> np.ndarray:
+        """The sky's light that reaches caller-given points (ptGatherSkyLight;
+        DESIGN.md §6 row 16), in the integrator's own units.  points: (n, 3).
+        lobe "cosine": gather_visibility's rays around `normals` (n, 3), for
+        irradiance at texels or vertices; lobe "sphere": rays uniform over the
+        sphere, normals unused (None), for a light probe.  Each open ray adds
+        the sky's radiance along it (CIE XYZ, at four wavelengths of its own
+        draw) times the nine real spherical harmonics of bands 0..2.  Returns
+        n SKY_RECORD_DTYPE records: SH (9, 3), OccludedMask, Unoccluded,
+        Samples; sky_irradiance (cosine) and sky_radiance_sh (sphere) read
+        them.  Blocks."""
+        s = (params or SkyGatherParameters(samples, radius, seed, offset, first_index, lobe)).as_struct()
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        nrm = None
+        if normals is not None:
+            nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+            if len(p) != len(nrm):
+                raise ValueError(f"{len(p)} points and {len(nrm)} normals")
+        elif s.Lobe == N.SKY_GATHER_COSINE:
+            raise ValueError("the cosine lobe needs normals")
+        out = np.zeros(len(p), dtype=SKY_RECORD_DTYPE)
+        hip("ptGatherSkyLight", self.device.handle, self._h, len(p), N.fptr(p), None if nrm is None else N.fptr(nrm),
+            C.byref(s), out.ctypes.data)
         return out
 
     def sample_textures(self, texture_index: np.ndarray, uv: np.ndarray, wrap: int = 0) -> np.ndarray:

@@ -10,7 +10,8 @@ import numpy as np
 from . import _native as N
 from ._core import camera_struct, guide_image, image, image_like, motion_table, pts, tile_grid
 from .params import (DenoiseParameters, DenoisePairParameters, DespikeParameters, RectifyParameters, ReprojectParameters,
-                     VisibilityGatherParameters)
+                     SkyGatherParameters, VisibilityGatherParameters)
+from .layout import SKY_RECORD_DTYPE
 
 
 class FrameStatistics:
@@ -261,6 +262,96 @@ def gather_visibility_reduce_host(samples: int, packed_velocities: np.ndarray, o
     pts("ptsGatherVisibilityReduce", samples, len(out), N.u32ptr(v), bits.view(np.uint64).ctypes.data_as(C.POINTER(C.c_uint64)),
         out.ctypes.data)
     return out
+
+
+def sky_gather_rays_host(points: np.ndarray, normals: "np.ndarray | None" = None,
+                         params: "SkyGatherParameters | None" = None):
+    """The rays DeviceScene.gather_sky_light traces and each ray's normalised
+    first wavelength L0, on the CPU (ptsSkyGatherRays, libptscene.so:
+    include/pt_visibility.h compiled for the host), bit for bit, for both
+    lobes.  points: (n, 3); normals: (n, 3), or None with the sphere lobe.
+    Returns (origins (n Samples, 3), packed velocities, durations, L0),
+    point-major."""
+    s = (params or SkyGatherParameters()).as_struct()
+    p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    nrm = None
+    if normals is not None:
+        nrm = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if len(p) != len(nrm):
+            raise ValueError(f"{len(p)} points and {len(nrm)} normals")
+    elif s.Lobe == N.SKY_GATHER_COSINE:
+        raise ValueError("the cosine lobe needs normals")
+    rays = len(p) * s.Samples if 1 <= s.Samples <= N.AMBIENT_OCCLUSION_MAX_SAMPLES else 0
+    o, v = np.zeros((rays, 3), np.float32), np.zeros(rays, np.uint32)
+    d, l0 = np.zeros(rays, np.float32), np.zeros(rays, np.float32)
+    pts("ptsSkyGatherRays", C.byref(s), len(p), N.fptr(p), None if nrm is None else N.fptr(nrm), N.fptr(o), N.u32ptr(v),
+        N.fptr(d), N.fptr(l0))
+    return o, v, d, l0
+
+
+def sky_gather_reduce_host(samples: int, packed_velocities: np.ndarray, occluded: np.ndarray,
+                           contributions: np.ndarray) -> np.ndarray:
+    """DeviceScene.gather_sky_light's records from any answer to "is ray r
+    blocked" over sky_gather_rays_host's rays and any per-ray XYZ
+    contributions (n samples, 3) (ptsSkyGatherReduce, libptscene.so): the
+    basis at the unpacked velocities, the 27 products per ray (an occluded
+    ray's contribution is taken as zero) and the device's summation tree.
+    Returns n SKY_RECORD_DTYPE records."""
+    samples = int(samples)
+    v = np.ascontiguousarray(packed_velocities, dtype=np.uint32).reshape(-1)
+    occ = np.ascontiguousarray(occluded, dtype=bool).reshape(-1)
+    c = np.ascontiguousarray(contributions, dtype=np.float32).reshape(-1, 3)
+    if samples < 1 or len(v) % samples or len(occ) != len(v) or len(c) != len(v):
+        raise ValueError(f"{len(v)} velocities, {len(occ)} bits and {len(c)} contributions for {samples} samples "
+                         f"per point")
+    bits = np.zeros((len(v) + 63) // 64 * 8, np.uint8)
+    packed_bits = np.packbits(occ, bitorder="little")
+    bits[:len(packed_bits)] = packed_bits
+    out = np.zeros(len(v) // samples, dtype=SKY_RECORD_DTYPE)
+    pts("ptsSkyGatherReduce", samples, len(out), N.u32ptr(v), bits.view(np.uint64).ctypes.data_as(C.POINTER(C.c_uint64)),
+        N.fptr(c), out.ctypes.data)
+    return out
+
+
+SH9_Y0 = 0.28209479   # the band-0 harmonic as the device has it (pt_sky_gather_basis' float literal)
+
+
+def sh9_basis(directions: np.ndarray) -> np.ndarray:
+    """The nine real spherical harmonics of bands 0..2 (z up, the order and
+    signs of pt_sky_gather_basis) at unit vectors (..., 3), in float64:
+    (..., 9)."""
+    d = np.asarray(directions, np.float64)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    k1, k2 = np.sqrt(3.0 / (4.0 * np.pi)), np.sqrt(15.0 / (4.0 * np.pi))
+    return np.stack([np.full_like(x, np.sqrt(1.0 / (4.0 * np.pi))), k1 * y, k1 * z, k1 * x, k2 * x * y, k2 * y * z,
+                     np.sqrt(5.0 / (16.0 * np.pi)) * (3.0 * z * z - 1.0), k2 * x * z, 0.5 * k2 * (x * x - y * y)],
+                    axis=-1)
+
+
+def sky_irradiance(records: np.ndarray) -> np.ndarray:
+    """The CIE XYZ irradiance from the sky at each point of cosine-lobe
+    records, (n, 3) float64: pi SH[0] / (Y0 Samples).  Without the pi it is
+    the pixel value the integrator converges to for direct sky light on a
+    white Lambertian surface there."""
+    r = np.asarray(records)
+    return np.pi * r["SH"][..., 0, :].astype(np.float64) / (SH9_Y0 * r["Samples"].astype(np.float64))[..., None]
+
+
+def sky_radiance_sh(records: np.ndarray) -> np.ndarray:
+    """The SH9 coefficients of the visible sky's radiance around each point
+    of sphere-lobe records, (n, 9, 3) float64: (4 pi / Samples) SH."""
+    r = np.asarray(records)
+    return 4.0 * np.pi * r["SH"].astype(np.float64) / r["Samples"].astype(np.float64)[..., None, None]
+
+
+def sh9_irradiance(coeffs: np.ndarray, normals: np.ndarray) -> np.ndarray:
+    """The irradiance on surfaces of unit normals (n, 3) under radiance given
+    by SH9 coefficients (9, C) or (n, 9, C): the clamped-cosine convolution,
+    sum_i A_band(i) coeffs[i] Y_i(normal) with A = pi, 2 pi / 3, pi / 4.
+    Returns (n, C) float64."""
+    A = np.array([np.pi] + [2.0 * np.pi / 3.0] * 3 + [np.pi / 4.0] * 5)
+    Y = sh9_basis(np.asarray(normals, np.float64).reshape(-1, 3))
+    return np.einsum("ni,ic->nc" if np.ndim(coeffs) == 2 else "ni,nic->nc", Y * A, np.asarray(coeffs, np.float64))
 
 
 def shape_surface_points(scene, shape_index: int):

@@ -18,9 +18,11 @@ from .device import Comm, Device, DeviceScene, device_count
 from .frame import DenoiseGuides, FrameHistory, SampleBuffer
 from .host import (FrameStatistics, denoise_host, denoise_pair_host, despike_host, frame_statistics_host,
                    gather_visibility_rays_host, gather_visibility_reduce_host, rectify_host, reproject_host,
-                   shape_motion, shape_surface_points, tile_mask_of_region, tile_statistics_host)
+                   sh9_basis, sh9_irradiance, shape_motion, shape_surface_points, sky_gather_rays_host,
+                   sky_gather_reduce_host, sky_irradiance, sky_radiance_sh, tile_mask_of_region, tile_statistics_host)
 from .params import (AmbientOcclusionParameters, DenoiseParameters, DenoisePairParameters, DespikeParameters,
-                     RectifyParameters, ReprojectParameters, ResolveParameters, VisibilityGatherParameters)
+                     RectifyParameters, ReprojectParameters, ResolveParameters, SkyGatherParameters,
+                     VisibilityGatherParameters)
 from .preview import PreviewParameters, PreviewRenderContext
 from .renderer import REFINE_MIN_ROUNDS, BasicRenderer, refine_tiles, render_until_noise
 

@@ -164,3 +164,31 @@ class VisibilityGatherParameters:
             raise ValueError(f"FirstIndex {self.FirstIndex} outside 0..2^32 - 1")
         return N.pt_visibility_gather_parameters(min(max(self.Samples, 0), 0xFFFFFFFF), self.Radius,
                                                  self.Seed & 0xFFFFFFFF, self.Offset, self.FirstIndex)
+
+
+class SkyGatherParameters:
+    """pt_sky_gather_parameters (pt_packed.h): VisibilityGatherParameters'
+    Samples, Radius, Seed, Offset and FirstIndex, with the same ranges, and
+    the Lobe the rays of DeviceScene.gather_sky_light are drawn from:
+    "cosine" (0; the cosine lobe around the point's normal, exactly
+    DeviceScene.gather_visibility's rays: irradiance) or "sphere" (1; uniform
+    over the sphere, no normal: a light probe).  DESIGN.md §6 row 16."""
+
+    LOBES = {"cosine": N.SKY_GATHER_COSINE, "sphere": N.SKY_GATHER_SPHERE}
+
+    def __init__(self, Samples: int = 16, Radius: float = float("inf"), Seed: int = 0, Offset: float = 1e-3,
+                 FirstIndex: int = 0, Lobe: "int | str" = "cosine"):
+        self.Samples, self.Radius, self.Seed = int(Samples), float(Radius), int(Seed)
+        self.Offset, self.FirstIndex = float(Offset), int(FirstIndex)
+        if isinstance(Lobe, str):
+            if Lobe not in self.LOBES:
+                raise ValueError(f"lobe {Lobe!r} is neither 'cosine' nor 'sphere'")
+            Lobe = self.LOBES[Lobe]
+        self.Lobe = int(Lobe)
+
+    def as_struct(self) -> N.pt_sky_gather_parameters:
+        # An out-of-range count or lobe reaches the library's check instead of ctypes' wrap-around.
+        if not 0 <= self.FirstIndex <= 0xFFFFFFFF:
+            raise ValueError(f"FirstIndex {self.FirstIndex} outside 0..2^32 - 1")
+        return N.pt_sky_gather_parameters(min(max(self.Samples, 0), 0xFFFFFFFF), self.Radius, self.Seed & 0xFFFFFFFF,
+                                          self.Offset, self.FirstIndex, min(max(self.Lobe, 0), 0xFFFFFFFF))

@@ -62,6 +62,11 @@
   hits of the 1920x1080 guide image at 16 samples, and 1 024 of them at 64 --
   with the wall time of the call beside the route without it (rays on the
   host, ptOccludedRays, host reduce); every kernel figure three times.
+* sky_gather (ptGatherSkyLight, occlusion.hip): the summed
+  kernel ms of a call's launches, at both lobes, beside ptGatherVisibility's
+  on the identical points in the same run, on gather's point sets of C2, C3
+  and C5, with the calls' wall times (four times the read-back); every figure
+  three times.
 * tiles (ptComputeTileStatistics, stats.hip, and ptSetBasicRendererActiveTiles;
   DESIGN.md §6 row 10): kernel ms of the per-tile statistics launch, single
   and pair, beside ptComputeFrameStatistics on the same buffers in the same
@@ -74,7 +79,7 @@
   on all of the job's threads, and the RGB -> spectrum table.
 
 Kernel times are HIP events on the device stream (ptGetKernelStats).
-Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|rectify|despike|specular_guides|occlusion|gather|preview|openpbr|host ...]
+Prints one JSON object.  usage: bench_next.py [resolve|denoise|stats|tiles|reproject|reproject_moving|rectify|despike|specular_guides|occlusion|gather|sky_gather|preview|openpbr|host ...]
 (default: all).
 """
 import json
@@ -816,6 +821,73 @@ def gather(pt, dev):
     return out
 
 
+def sky_gather(pt, dev):
+    """Per config (C2, C3, C5) and point set (gather's: guide_hits_s16 and
+    probes_1024_s64) -- sky_cosine_kernel_ms, sky_sphere_kernel_ms: the summed
+    kernel time of one ptGatherSkyLight call's launches at each lobe;
+    visibility_kernel_ms: ptGatherVisibility's on the identical points and
+    parameters in the same run (at the cosine lobe the identical rays), the
+    stats reset between the legs; each a list: the mean of 3 timed calls
+    after a warm-up call, taken three times in turn.  cosine_ratio,
+    sphere_ratio: the ratio of the medians; visibility_spread: (max - min) /
+    median of the comparator's own three figures.  *_wall_ms: the wall time
+    of a call (upload, launches, read-back of 128 or 32 bytes per point).
+    open_share_*: the share of rays that look the sky up.  masks_equal: the
+    cosine records' masks against ptGatherVisibility's."""
+    out = {}
+    W, H = 1920, 1080
+
+    def leg(fn, reps):
+        dev.synchronize()
+        dev.reset_kernel_stats()
+        dev.set_profiling(True, period=1)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        dev.synchronize()
+        wall = time.perf_counter() - t0
+        n, ms = dev.kernel_stats(K_EXTEND)
+        dev.set_profiling(False)
+        return ms / reps, n // reps, wall / reps * 1e3
+
+    for cid in (2, 3, 5):
+        scene = pt.Scene.config(cid)
+        ds = pt.DeviceScene(dev)
+        ds.update(scene)
+        P, Nr = guide_hit_points(pt, dev, ds, W, H)
+        pick = np.linspace(0, len(P) - 1, 1024).astype(np.int64)
+        sets = {"guide_hits_s16": (P, Nr, 16), "probes_1024_s64": (P[pick], Nr[pick], 64)}
+        for name, (p, n, S) in sets.items():
+            vis = ds.gather_visibility(p, n, S, float("inf"), 3)   # warm
+            cos = ds.gather_sky_light(p, n, S, float("inf"), 3, lobe="cosine")
+            sph = ds.gather_sky_light(p, None, S, float("inf"), 3, lobe="sphere")
+            res = {"points": len(p), "samples": S, "extend_form": ds.extend_form,
+                   "masks_equal": bool(np.array_equal(cos["OccludedMask"], vis["OccludedMask"])),
+                   "open_share_cosine": round(float(cos["Unoccluded"].sum() / cos["Samples"].sum()), 4),
+                   "open_share_sphere": round(float(sph["Unoccluded"].sum() / sph["Samples"].sum()), 4),
+                   "launches_per_call": None}
+            del vis, cos, sph
+            legs = {"visibility": lambda: ds.gather_visibility(p, n, S, float("inf"), 3),
+                    "sky_cosine": lambda: ds.gather_sky_light(p, n, S, float("inf"), 3, lobe="cosine"),
+                    "sky_sphere": lambda: ds.gather_sky_light(p, None, S, float("inf"), 3, lobe="sphere")}
+            for key in legs:
+                res[key + "_kernel_ms"], res[key + "_wall_ms"] = [], []
+            for _ in range(3):
+                for key, fn in legs.items():
+                    ms, launches, wall = leg(fn, 3)
+                    res[key + "_kernel_ms"].append(round(ms, 4))
+                    res[key + "_wall_ms"].append(round(wall, 3))
+                    res["launches_per_call"] = launches
+            med = float(np.median(res["visibility_kernel_ms"]))
+            res["cosine_ratio"] = round(float(np.median(res["sky_cosine_kernel_ms"])) / med, 4)
+            res["sphere_ratio"] = round(float(np.median(res["sky_sphere_kernel_ms"])) / med, 4)
+            res["visibility_spread"] = round((max(res["visibility_kernel_ms"]) - min(res["visibility_kernel_ms"])) / med, 4)
+            out[f"c{cid}_{name}"] = res
+        ds.close()
+        scene.close()
+    return out
+
+
 def preview(pt, dev):
     out = {}
     modes = {"base_color": pt.PREVIEW_RENDER_MODE_BASE_COLOR, "shaded": pt.PREVIEW_RENDER_MODE_BASE_COLOR_SHADED,
@@ -897,7 +969,7 @@ def main():
     pt = load()
     entries = {"resolve": resolve, "denoise": denoise, "stats": stats, "tiles": tiles, "reproject": reproject, "reproject_moving": reproject_moving,
                "rectify": rectify, "despike": despike, "specular_guides": specular_guides, "occlusion": occlusion,
-               "gather": gather, "preview": preview, "openpbr": openpbr}
+               "gather": gather, "sky_gather": sky_gather, "preview": preview, "openpbr": openpbr}
     want = sys.argv[1:] or list(entries) + ["host"]
     dev = pt.Device(0)
     res = {name: fn(pt, dev) for name, fn in entries.items() if name in want}
