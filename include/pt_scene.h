@@ -356,6 +356,15 @@ double ptsStatsNoise(const pt_frame_statistics* stats, double q);
  * argument. */
 uint32_t ptsRayKey(const float origin[3], const float velocity[3], const float lo[3], const float hi[3]);
 
+/* pt_facetest.h's lean face test from the determinant on, over n operand
+ * sets: u, w, t = (1 / det) * num_u, num_w, num_t, with 1 / det taken as the
+ * device takes it (the fast reciprocal's Newton step inside its range, the
+ * IEEE quotient where pt_face_needs_division asks for it), and miss[i] the
+ * folded flag pt_face_miss against time[i]; divides[i] is what
+ * pt_face_needs_division answered for det[i].  0, or -1 on a NULL argument. */
+int ptsFaceTest(uint32_t n, const float* det, const float* num_u, const float* num_w, const float* num_t,
+                const float* time, uint32_t* miss, float* u, float* w, float* t, uint32_t* divides);
+
 #ifdef __cplusplus
 }
 #endif

@@ -433,6 +433,7 @@ SCENE_API = {
     "ptsStatsAutoBrightness": (C.c_double, [C.POINTER(pt_frame_statistics), C.c_double, C.c_double, C.c_double]),
     "ptsStatsNoise": (C.c_double, [C.POINTER(pt_frame_statistics), C.c_double]),
     "ptsRayKey": (_u32, [_fptr, _fptr, _fptr, _fptr]),
+    "ptsFaceTest": (_i32, [_u32, _fptr, _fptr, _fptr, _fptr, _fptr, _u32ptr, _fptr, _fptr, _fptr, _u32ptr]),
 }
 
 HIP_API = {

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include "../../../include/pt_glsl.h"
 #include "../../../include/pt_packed.h"
+#include "../../../include/pt_facetest.h"
 
 #define PT_DEV __device__ __forceinline__
 
@@ -175,14 +176,16 @@ PT_DEV float FastRcp(float d)
     return __builtin_fmaf(e, y, y);
 }
 
-// Not used by the traversal: it measured 1 % slower on C3 extend than the
-// IEEE division sequence (round 2); ptCheckFastReciprocal keeps
-// its bit-equality checked.
+// The face test's 1 / Det (FaceTest, traverse.hpp; its gate is pt_facetest.h's
+// pt_face_needs_division).  Round 2 measured it 1 % slower on C3 extend than
+// the IEEE division sequence, when the loop followed its dependent-step
+// latency; since the loop runs near the VALU issue rate the seven instructions
+// fewer pay (DESIGN §4 "Lean extend").
 
 PT_DEV bool FastRcpRange(float d)
 {
     float m = pt_abs(d);
-    return (m >= 0x1p-126f) & (m < 0x1p126f);
+    return (m >= PT_FAST_RCP_MIN) & (m < PT_FAST_RCP_MAX);
 }
 
 

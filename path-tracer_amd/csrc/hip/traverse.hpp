@@ -168,31 +168,48 @@ PT_DEV void UnpackVertexIndices(uint32_t A, uint32_t B, uint32_t& v0, uint32_t& 
     v2 = B >> 10;
 }
 
+// OFF32 (the u16 stack's scenes: every face index is below 2^15,
+// BlasWords16FirstBits): the face's byte offset is a 24-bit product in one
+// register beside the scalar base, instead of a 64-bit address per lane.
+//
+// 1 / Det is FastRcp where that is the IEEE quotient (pt_facetest.h:
+// 2^-126 <= |Det| < 2^126, or a face missed whatever the quotient); the lanes
+// outside (huge or NaN determinants) divide in a block the wave enters only
+// when one of its lanes needs it.  The reference's early returns are one
+// predicate (no value depends on which test failed first), folded to four
+// compares (pt_face_miss); U, W and T come out of the reference's operations
+// in its order.
+template <bool OFF32 = false>
 PT_DEV bool FaceTest(const dscene& S, uint32_t F, const lane_state& L, bool valid, float& T, float& U, float& W,
                      uint32_t& VA, uint32_t& VB)
 {
     // valid == false (an empty leaf): face 0 is read and the test forced to
     // miss, instead of a branch around the call.
     uint32_t Fl = valid ? F : 0u;
-    const float4* Fp = S.mesh_faces + 3 * (size_t)Fl;   // one address, immediate offsets
+    const float4* Fp = OFF32 ? (const float4*)((const char*)S.mesh_faces + __umul24(Fl, 48u))
+                             : S.mesh_faces + 3 * (size_t)Fl;   // one address, immediate offsets
     float4 a = Fp[0], b = Fp[1], c = Fp[2];
     pt3 P0 = xyz(a);
     pt3 Edge1 = xyz(b);
     pt3 Edge2 = xyz(c);
     PackVertexIndices(__float_as_uint(a.w), __float_as_uint(b.w), __float_as_uint(c.w), VA, VB);
-    // Every quantity is evaluated with the reference's operations and
-    // operand order; its early returns become one predicate (no value
-    // depends on which test failed first), so the exits collapse into a
-    // single select.
     pt3 RCE2 = cross(L.V, Edge2);
     float Det = dot(Edge1, RCE2);
-    float InvDet = 1.0f / Det;
+    float InvDet = FastRcp(Det);
+    const bool divide = pt_face_needs_division(Det);
+    if (__builtin_amdgcn_ballot_w64(divide) != 0) {
+        // (The empty asm keeps the division inside the block: without it the
+        // compiler evaluates both forms on every step and selects.)
+        float d = Det;
+        asm volatile("" : "+v"(d));
+        if (divide) InvDet = 1.0f / d;
+    }
     pt3 Sv = L.O - P0;
     U = InvDet * dot(Sv, RCE2);
     pt3 SCE1 = cross(Sv, Edge1);
     W = InvDet * dot(L.V, SCE1);
     T = InvDet * dot(Edge2, SCE1);
-    return (pt_abs(Det) < PT_EPSILON) | (U < 0) | (U > 1) | (W < 0) | (U + W > 1) | (T < 0) | (T > L.Time) | !valid;
+    return (pt_face_miss(Det, U, W, T, L.Time) != 0) | !valid;
 }
 
 PT_DEV void LaneMeshFace(const dscene& S, uint32_t F, lane_state& L, bool valid = true)
@@ -446,7 +463,7 @@ PT_DEV bool LaneStep(const dscene& S, lane_state& L, tstack<SPILL, CAP, SE>& st,
         asm("" : "=v"(fT), "=v"(fU), "=v"(fW), "=v"(TA), "=v"(TB), "=v"(fVA), "=v"(fVB));
         asm("" : "=v"(aw0), "=v"(aw1), "=v"(bw0), "=v"(bw1));
         if (face) {
-            fmiss = FaceTest(S, L.na, L, L.na < L.nb, fT, fU, fW, fVA, fVB);   // (an empty leaf tests nothing)
+            fmiss = FaceTest<sizeof(SE) == 2>(S, L.na, L, L.na < L.nb, fT, fU, fW, fVA, fVB);   // (an empty leaf tests nothing)
             ss.face_step(L.na + 1 >= L.nb);
         } else {
             ss.node(true);
@@ -567,6 +584,22 @@ PT_DEV bool LaneStep(const dscene& S, lane_state& L, tstack<SPILL, CAP, SE>& st,
 // parameter, the stack indexed by dB alone and the lane complete at "not
 // moved and the stack empty".  Hit.ShapeIndex stays 0xFFFFFFFE on a face hit;
 // the caller sets it to shape 0 after its loop (TlasStep's BLAS exit).
+// The joined update gives every lane LaneStep's results, but forms its flags
+// from the compares' wave masks in scalar registers and skips a half's part
+// on a wave step without a lane of that half (DESIGN §4 "Lean extend").
+
+// A compare as the wave's mask in a scalar register pair (bit = lane, 0 for a
+// lane that is not active), and a mask back as a per-lane flag: flags that
+// combine several compares are then formed by scalar instructions, where
+// `bool` expressions that cross a branch cost a 0 / 1 lane value and a
+// compare each.
+PT_DEV unsigned long long PtMaskNeU(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 33); }
+PT_DEV unsigned long long PtMaskEqU(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 32); }
+PT_DEV unsigned long long PtMaskLtU(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 36); }
+PT_DEV unsigned long long PtMaskGtF(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 2); }   // ordered
+PT_DEV unsigned long long PtMaskLtF(float a, float b) { return __builtin_amdgcn_fcmpf(a, b, 4); }   // ordered
+PT_DEV unsigned long long PtActive() { return __builtin_amdgcn_ballot_w64(true); }
+PT_DEV bool PtLanes(unsigned long long m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 
 PT_DEV void MeshBegin(const dscene& S, lane_state& L, pt3 O, pt3 V, float Duration)
 {
@@ -589,7 +622,8 @@ PT_DEV bool MeshStep(const dscene& S, lane_state& L, tstack<SPILL, CAP, SE>& st)
 {
     // (See LaneStep for why the divergent halves compute fresh values only
     // and every state update is a select after the join.)
-    const bool face = L.nb > 0;
+    const unsigned long long mF = PtMaskNeU(L.nb, 0u);   // the wave's face lanes
+    const bool face = PtLanes(mF);
     bool fmiss = true;
     float fT, fU, fW, TA, TB;
     uint32_t aw0, aw1, bw0, bw1, fVA, fVB;
@@ -597,10 +631,21 @@ PT_DEV bool MeshStep(const dscene& S, lane_state& L, tstack<SPILL, CAP, SE>& st)
     asm("" : "=v"(fT), "=v"(fU), "=v"(fW), "=v"(TA), "=v"(TB), "=v"(fVA), "=v"(fVB));
     asm("" : "=v"(aw0), "=v"(aw1), "=v"(bw0), "=v"(bw1));
     if (face) {
-        fmiss = FaceTest(S, L.na, L, L.na < L.nb, fT, fU, fW, fVA, fVB);
+        fmiss = FaceTest<sizeof(SE) == 2>(S, L.na, L, L.na < L.nb, fT, fU, fW, fVA, fVB);
     } else {
         float4 a0, a1, b0, b1;
-        if (L.na < st.ncn) {
+        if (sizeof(SE) == 2) {
+            // The u16 stack's scenes hold pair indices below 2^15: one 32-bit
+            // byte offset serves the LDS copy and the scalar-based global load.
+            const uint32_t off = L.na * 32u;
+            if (L.na < st.ncn) {
+                const PT_LDS f32x4* Cp = (const PT_LDS f32x4*)((const PT_LDS char*)st.nc + off);
+                a0 = F4(Cp[0]); a1 = F4(Cp[1]); b0 = F4(Cp[2]); b1 = F4(Cp[3]);
+            } else {
+                const PT_GLOBAL f32x4* Np = (const PT_GLOBAL f32x4*)((const PT_GLOBAL char*)S.mesh_nodes + off);
+                a0 = F4(Np[0]); a1 = F4(Np[1]); b0 = F4(Np[2]); b1 = F4(Np[3]);
+            }
+        } else if (L.na < st.ncn) {
             const PT_LDS f32x4* Cp = (const PT_LDS f32x4*)st.nc + 2 * L.na;
             a0 = F4(Cp[0]); a1 = F4(Cp[1]); b0 = F4(Cp[2]); b1 = F4(Cp[3]);
         } else {
@@ -611,27 +656,43 @@ PT_DEV bool MeshStep(const dscene& S, lane_state& L, tstack<SPILL, CAP, SE>& st)
         aw0 = __float_as_uint(a0.w), aw1 = __float_as_uint(a1.w);
         bw0 = __float_as_uint(b0.w), bw1 = __float_as_uint(b1.w);
     }
-    L.Time = fmiss ? L.Time : fT;
-    L.Shape = fmiss ? L.Shape : 0xFFFFFFFEu;
-    L.Prim = fmiss ? L.Prim : L.na;
-    L.HA = fmiss ? L.HA : fVA;
-    L.HB = fmiss ? L.HB : fVB;
-    L.C = v3(fmiss ? L.C.x : 1 - fU - fW, fmiss ? L.C.y : fU, fmiss ? L.C.z : fW);
-    bool goB = TA > TB;
-    float Tfar = goB ? TA : TB;
-    bool push = !face & (Tfar < PT_INFINITY);
-    bool moved = (face & (L.na + 1 < L.nb)) | (!face & (goB | (TA < PT_INFINITY)));
-    if (push & (L.dB < 32)) {
-        st.put(L.dB++, BlasPush<SE>(S, goB ? aw0 : bw0, goB ? aw1 : bw1, pair + (goB ? 0u : 1u)));
+    // Each half's part of the joined update runs only on a wave step that has
+    // a lane of that half (scalar branches on the wave's masks; the lanes'
+    // results are those of the selects either way).
+    const bool anyF = mF != 0, anyI = (PtActive() & ~mF) != 0;
+    if (anyF) {
+        L.Time = fmiss ? L.Time : fT;
+        L.Shape = fmiss ? L.Shape : 0xFFFFFFFEu;
+        L.Prim = fmiss ? L.Prim : L.na;
+        L.HA = fmiss ? L.HA : fVA;
+        L.HB = fmiss ? L.HB : fVB;
+        L.C = v3(fmiss ? L.C.x : 1 - fU - fW, fmiss ? L.C.y : fU, fmiss ? L.C.z : fW);
     }
-    uint32_t na = face ? L.na + 1 : (goB ? bw0 : aw0);
-    uint32_t nb = face ? L.nb : (goB ? bw1 : aw1);
+    // A face lane moves on to its leaf's next face; an internal lane takes
+    // the reference's three-way decision (LaneStep).  The flags are the
+    // compares' wave masks combined in scalar registers (a compare leaves 0
+    // for a lane that is not active, so ~mF never adds one).
+    uint32_t na = L.na + 1;
+    uint32_t nb = L.nb;
+    unsigned long long mMoved = mF & PtMaskLtU(na, nb);
+    if (anyI) {
+        const unsigned long long mB = PtMaskGtF(TA, TB);
+        const bool goB = PtLanes(mB);
+        const float Tfar = goB ? TA : TB;
+        mMoved |= ~mF & (mB | PtMaskLtF(TA, PT_INFINITY));
+        if (PtLanes(~mF & PtMaskLtF(Tfar, PT_INFINITY) & PtMaskLtU(L.dB, 32u))) {
+            st.put(L.dB++, BlasPush<SE>(S, goB ? aw0 : bw0, goB ? aw1 : bw1, pair + (goB ? 0u : 1u)));
+        }
+        na = face ? na : (goB ? bw0 : aw0);
+        nb = face ? nb : (goB ? bw1 : aw1);
+    }
     // The lane's end is mask logic beside the pop, not an exit inside the
     // `!moved` branch: with the exit nested there the compiler split the loop
     // in two and the lanes that need a pop waited until no lane of the wave
     // was still moving.
-    const bool pop = !moved & (L.dB > 0);
-    const bool done = !moved & (L.dB == 0);
+    const unsigned long long mEmpty = PtMaskEqU(L.dB, 0u);
+    const bool pop = PtLanes(~mMoved & ~mEmpty & PtActive());
+    const bool done = PtLanes(~mMoved & mEmpty);
     if (pop) BlasPop<SE>(S, st.get(--L.dB), na, nb);
     L.na = na;
     L.nb = nb;

@@ -5,6 +5,7 @@
 #include "image.hpp"
 #include "../../../include/pt_scene.h"
 #include "../../../include/pt_raykey.h"
+#include "../../../include/pt_facetest.h"
 
 #include <cstring>
 #include <exception>
@@ -415,6 +416,36 @@ int ptsLoadSpectrumTable(const char* path)
 }
 
 void ptsSetSpectrumTablePath(const char* path) { SetSpectrumTablePath(path ? path : ""); }
+
+// The device's lean face test (FaceTest, traverse.hpp) from the determinant on,
+// over n operand sets: the three numerators times 1 / Det, then pt_facetest.h's
+// miss flag.  1 / Det is the IEEE quotient where pt_face_needs_division says
+// so, else the fast reciprocal's Newton step on a seed; the host's seed is the
+// correctly rounded quotient (the device's is v_rcp_f32, within 1 ulp of it;
+// the step's result is held to the quotient over every bit pattern by
+// ptCheckFastReciprocal).  divides[i] is the gate's own answer for det[i].
+// Returns 0, or -1 on a NULL argument.
+int ptsFaceTest(uint32_t n, const float* det, const float* num_u, const float* num_w, const float* num_t,
+                const float* time, uint32_t* miss, float* u, float* w, float* t, uint32_t* divides)
+{
+    if (!det || !num_u || !num_w || !num_t || !time || !miss || !u || !w || !t || !divides) return -1;
+    for (uint32_t i = 0; i < n; i++) {
+        const float d = det[i];
+        float inv;
+        divides[i] = (uint32_t)pt_face_needs_division(d);
+        if (divides[i]) {
+            inv = 1.0f / d;
+        } else {
+            const float y = 1.0f / d;
+            inv = pt_fma(pt_fma(-d, y, 1.0f), y, y);
+        }
+        u[i] = inv * num_u[i];
+        w[i] = inv * num_w[i];
+        t[i] = inv * num_t[i];
+        miss[i] = (uint32_t)pt_face_miss(d, u[i], w[i], t[i], time[i]);
+    }
+    return 0;
+}
 
 // pt_raykey.h's key of one ray over the grid of the bounds [lo, hi].
 uint32_t ptsRayKey(const float origin[3], const float velocity[3], const float lo[3], const float hi[3])
