@@ -38,8 +38,10 @@ def _round_half_away(x: np.ndarray) -> np.ndarray:
 
 
 def pack_snorm2x16(p: np.ndarray) -> np.ndarray:
-    """glm::packSnorm2x16 / GLSL packSnorm2x16: round(clamp(v,-1,1)*32767)."""
-    c = np.clip(p.astype(np.float32), np.float32(-1), np.float32(1)) * np.float32(32767.0)
+    """glm::packSnorm2x16 / GLSL packSnorm2x16: round(clamp(v,-1,1)*32767).
+    The clamp is min(max(v, -1), 1) on minNum / maxNum, so a NaN packs as -1
+    (np.clip would hand the NaN on to the integer cast)."""
+    c = np.fmin(np.fmax(p.astype(np.float32), np.float32(-1)), np.float32(1)) * np.float32(32767.0)
     q = _round_half_away(c.astype(np.float32)).astype(np.int64) & 0xFFFF
     return (q[..., 0] | (q[..., 1] << 16)).astype(np.uint32)
 

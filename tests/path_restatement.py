@@ -535,6 +535,8 @@ def _refraction_terms(In, Out, rel, a, cin, cout, d0=None, n0=None):
     out = []
     for k in range(4):
         t = cin[k] * rel[k] + cout[k]
+        if t == 0:
+            STATS["sq_zero"] += 1   # relative IOR 1: J = |cout| / 0
         j = abs(cout[k]) / (t * t)
         out.append((((d[k] * (one - f[k])) * gm) * j) * abs(cin[k] / In[2]))
     return out
@@ -876,12 +878,17 @@ def scatter(W_, sl, g, hit, ptp):
                 if sl.active[i] == NONE:
                     sl.active[i] = shape
                     break
+            else:
+                STATS["active_full"] += 1   # a fifth shape entered: not recorded
         else:
             for i in range(4):
                 if sl.active[i] == shape:
                     sl.active[i] = NONE
                     break
+            if sl.active[0] == NONE and any(a != NONE for a in sl.active[1:]):
+                STATS["slot0_hole"] += 1
     if g.r01() < ptp:
+        STATS["terminated"] += 1
         return False, None, None
     sl.prob = [p * (f32(1.0) - ptp) for p in sl.prob]
     v2 = [(inn[0] * TX[i] + inn[1] * TY[i]) + inn[2] * N[i] for i in range(3)]
