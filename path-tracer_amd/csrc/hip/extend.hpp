@@ -90,7 +90,8 @@ constexpr bool kRendererSource = std::is_same<Src, ray_source_slots>::value;
 // MESH (a dscene::single_mesh scene): the mesh-only loop instead, one pass
 // for the lanes whose ray takes the exact fast division and one for the
 // others (usually none); each lane's ray is traced as before, only beside
-// other lanes.
+// other lanes.  The loops carry the hit's time and face; MeshEnd forms the
+// rest of the record once, after them.
 //
 // TRAIN (the renderer's mesh-only loop in LENGTH order, on the table's
 // training rounds): the lane counts its steps and adds them, capped at 255,
@@ -114,7 +115,7 @@ PT_DEV void ExtendRay(const dscene& S, const Src& src, tstack<SPILL, CAP, E>& st
             } else {
                 while (!MeshStep<false>(S, Ln, st)) steps++;
             }
-            if (Ln.Shape == 0xFFFFFFFEu) Ln.Shape = 0;
+            MeshEnd<sizeof(E) == 2>(S, Ln);
             if ((slot & 255u) >= src.L.len_cam[slot >> 8]) {
                 // The ray again from its record: nothing of it stays live over the loop.
                 const float4 r = src.L.ray[slot];
@@ -130,7 +131,7 @@ PT_DEV void ExtendRay(const dscene& S, const Src& src, tstack<SPILL, CAP, E>& st
             } else {
                 while (!MeshStep<false>(S, Ln, st)) {}
             }
-            if (Ln.Shape == 0xFFFFFFFEu) Ln.Shape = 0;
+            MeshEnd<sizeof(E) == 2>(S, Ln);
         } else {
             LaneBegin(S, Ln, O, V, D);
             no_stats ns;

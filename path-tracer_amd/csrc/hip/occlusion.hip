@@ -52,8 +52,9 @@ struct ray_source_held {
 // Whether anything lies on (O, V) within D.  The lane's stack starts empty
 // (LaneBegin / MeshBegin zero the depths; an entry is put before it is read,
 // spill rows included).  MESH: the mesh-only loop of a dscene::single_mesh
-// scene, in ExtendRay's two passes.  Of the hit only Shape is read afterwards:
-// Prim, C, HA and HB are dead and the compiler drops them.
+// scene, in ExtendRay's two passes; its "hit" is MeshHit (the loop carries the
+// hit's face, not its shape).  Of the general loop's hit only Shape is read
+// afterwards: Prim, C, HA and HB are dead and the compiler drops them.
 template <bool SPILL, int CAP, class E, bool MESH, class Src, class Stats>
 PT_DEV bool AnyHit(const dscene& S, tstack<SPILL, CAP, E>& st, const Src& src, uint32_t slot, pt3 O, pt3 V, float D,
                    Stats& ss)
@@ -62,10 +63,11 @@ PT_DEV bool AnyHit(const dscene& S, tstack<SPILL, CAP, E>& st, const Src& src, u
     if constexpr (MESH) {
         MeshBegin(S, Ln, O, V, D);
         if (Ln.exact) {
-            while (Ln.Shape == SHAPE_INDEX_NONE && !MeshStep<true>(S, Ln, st)) {}
+            while (!MeshHit(Ln) && !MeshStep<true>(S, Ln, st)) {}
         } else {
-            while (Ln.Shape == SHAPE_INDEX_NONE && !MeshStep<false>(S, Ln, st)) {}
+            while (!MeshHit(Ln) && !MeshStep<false>(S, Ln, st)) {}
         }
+        return MeshHit(Ln);   // (the mesh-only loop keeps the hit's face, not Shape: no MeshEnd needed)
     } else {
         LaneBegin(S, Ln, O, V, D);
         if (S.g.ShapeCount != 0) {

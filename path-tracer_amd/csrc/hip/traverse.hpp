@@ -46,12 +46,16 @@ struct tstack {
 // so every ray reaches the same closest hit bit for bit.  One flat loop over
 // both levels keeps a single loop-carried state (no nested divergent loops).
 
+// No face: the mesh-only loop's "nothing hit yet" in lane_state::Prim (MeshStep).
+// Never a face index (a face record is 48 bytes) and never stored in a record.
+#define PT_FACE_NONE 0xFFFFFFFFu
+
 struct lane_state {
     pt3 O, V, Y;         // current-level ray (world at TLAS level, object space
                          // inside a mesh) and its reciprocal velocity
     float Time;          // Hit.Time
     uint32_t Shape;      // Hit.ShapeIndex (0xFFFFFFFE = face of the current mesh)
-    uint32_t Prim;       // Hit.PrimitiveIndex
+    uint32_t Prim;       // Hit.PrimitiveIndex (mesh-only loop: PT_FACE_NONE until a face is hit)
     pt3 C;               // Hit.PrimitiveCoordinates
     uint32_t na, nb;     // node being processed: TLAS {ChildNodeIndices, ShapeIndex},
                          // BLAS {FaceBeginOrNodeIndex, FaceEndIndex}
@@ -151,7 +155,9 @@ PT_DEV void IntersectAnalytic(int32_t Type, pt3 O, pt3 V, uint32_t ShapeIndex, l
 // the edges are the reference's `Position1 - Position0`, `Position2 -
 // Position0`, subtracted once on the host at upload in the same IEEE
 // arithmetic, so every later operation sees identical operands.
-// The test itself: miss flag, T and the coordinates U, W; L is only read.
+// The test itself: miss flag, T, the coordinates U, W and the face's three
+// vertex index words as loaded (a caller that reads none of them pays nothing
+// for them); L is only read.
 // A face's three vertex indices in 64 bits (21 bits each; dscene::vidx21
 // scenes, whose vertex count fits): the hit record carries them to shade,
 // which then reads the vertices without first reading the face.
@@ -181,7 +187,7 @@ PT_DEV void UnpackVertexIndices(uint32_t A, uint32_t B, uint32_t& v0, uint32_t& 
 // in its order.
 template <bool OFF32 = false>
 PT_DEV bool FaceTest(const dscene& S, uint32_t F, const lane_state& L, bool valid, float& T, float& U, float& W,
-                     uint32_t& VA, uint32_t& VB)
+                     uint32_t& I0, uint32_t& I1, uint32_t& I2)
 {
     // valid == false (an empty leaf): face 0 is read and the test forced to
     // miss, instead of a branch around the call.
@@ -192,7 +198,7 @@ PT_DEV bool FaceTest(const dscene& S, uint32_t F, const lane_state& L, bool vali
     pt3 P0 = xyz(a);
     pt3 Edge1 = xyz(b);
     pt3 Edge2 = xyz(c);
-    PackVertexIndices(__float_as_uint(a.w), __float_as_uint(b.w), __float_as_uint(c.w), VA, VB);
+    I0 = __float_as_uint(a.w), I1 = __float_as_uint(b.w), I2 = __float_as_uint(c.w);
     pt3 RCE2 = cross(L.V, Edge2);
     float Det = dot(Edge1, RCE2);
     float InvDet = FastRcp(Det);
@@ -215,8 +221,9 @@ PT_DEV bool FaceTest(const dscene& S, uint32_t F, const lane_state& L, bool vali
 PT_DEV void LaneMeshFace(const dscene& S, uint32_t F, lane_state& L, bool valid = true)
 {
     float T, U, W;
-    uint32_t VA, VB;
-    bool miss = FaceTest(S, F, L, valid, T, U, W, VA, VB);
+    uint32_t I0, I1, I2, VA, VB;
+    bool miss = FaceTest(S, F, L, valid, T, U, W, I0, I1, I2);
+    PackVertexIndices(I0, I1, I2, VA, VB);
     // Selects, not a branch: the hit registers are updated in place (a
     // conditional update made the compiler keep and copy a second set).
     L.Time = miss ? L.Time : T;
@@ -463,7 +470,9 @@ PT_DEV bool LaneStep(const dscene& S, lane_state& L, tstack<SPILL, CAP, SE>& st,
         asm("" : "=v"(fT), "=v"(fU), "=v"(fW), "=v"(TA), "=v"(TB), "=v"(fVA), "=v"(fVB));
         asm("" : "=v"(aw0), "=v"(aw1), "=v"(bw0), "=v"(bw1));
         if (face) {
-            fmiss = FaceTest<sizeof(SE) == 2>(S, L.na, L, L.na < L.nb, fT, fU, fW, fVA, fVB);   // (an empty leaf tests nothing)
+            uint32_t I0, I1, I2;
+            fmiss = FaceTest<sizeof(SE) == 2>(S, L.na, L, L.na < L.nb, fT, fU, fW, I0, I1, I2);   // (an empty leaf tests nothing)
+            PackVertexIndices(I0, I1, I2, fVA, fVB);
             ss.face_step(L.na + 1 >= L.nb);
         } else {
             ss.node(true);
@@ -582,8 +591,13 @@ PT_DEV bool LaneStep(const dscene& S, lane_state& L, tstack<SPILL, CAP, SE>& st,
 // the first (TLAS leaf) step, from kernel arguments; MeshStep is LaneStep's
 // FACE_STEP BLAS half, operation for operation, with `exact` a template
 // parameter, the stack indexed by dB alone and the lane complete at "not
-// moved and the stack empty".  Hit.ShapeIndex stays 0xFFFFFFFE on a face hit;
-// the caller sets it to shape 0 after its loop (TlasStep's BLAS exit).
+// moved and the stack empty".
+// Of the hit, the loop carries only Hit.Time and the face (L.Prim, PT_FACE_NONE
+// until a face is hit: a sentinel, so face 0 is a hit like any other): a face
+// lane's step updates those two, and the other attributes, which the record
+// needs of one face per ray, are formed after the loop (MeshEnd).  The face
+// kept is the one LaneStep would have left in Prim -- each accepted face
+// replaces the last, a tie included -- so the record is the same.
 // The joined update gives every lane LaneStep's results, but forms its flags
 // from the compares' wave masks in scalar registers and skips a half's part
 // on a wave step without a lane of that half (DESIGN §4 "Lean extend").
@@ -604,17 +618,42 @@ PT_DEV bool PtLanes(unsigned long long m) { return __builtin_amdgcn_inverse_ball
 PT_DEV void MeshBegin(const dscene& S, lane_state& L, pt3 O, pt3 V, float Duration)
 {
     L.Time = Duration;
-    L.Shape = SHAPE_INDEX_NONE;
-    L.Prim = 0;
-    L.C = v3s(0);
-    L.HA = 0;
-    L.HB = 0;
+    L.Prim = PT_FACE_NONE;
     L.dT = 0;
     L.dB = 0;
     L.blas = 0;
     SetLevelRay(S, L, mat4_mul_point(S.mesh_from, O), mat4_mul_vector(S.mesh_from, V));
     L.na = S.mesh_root[0];
     L.nb = S.mesh_root[1];
+}
+
+// Whether the mesh-only loop has accepted a face so far.
+PT_DEV bool MeshHit(const lane_state& L) { return L.Prim != PT_FACE_NONE; }
+
+// The mesh-only loop's hit record, after the loop: a lane that hit evaluates
+// its face once more through FaceTest -- the same operations on the same
+// operands (the face, and the lane's mesh-space O and V, unchanged since
+// MeshBegin), the same reciprocal or division, so U and W are the bits the
+// loop's test had -- and takes the coordinates and the packed vertex indices
+// from it; Hit.Time is the loop's.  A miss leaves LaneBegin's record.  The
+// shape is the scene's only one, 0 (TlasStep's BLAS exit).
+template <bool OFF32>
+PT_DEV void MeshEnd(const dscene& S, lane_state& L)
+{
+    const bool hit = MeshHit(L);
+    L.Shape = hit ? 0u : SHAPE_INDEX_NONE;
+    L.C = v3s(0);
+    L.HA = 0;
+    L.HB = 0;
+    if (hit) {
+        float T, U, W;
+        uint32_t I0, I1, I2;
+        FaceTest<OFF32>(S, L.Prim, L, true, T, U, W, I0, I1, I2);
+        PackVertexIndices(I0, I1, I2, L.HA, L.HB);
+        L.C = v3(1 - U - W, U, W);
+    } else {
+        L.Prim = 0;
+    }
 }
 
 template <bool EXACT, bool SPILL, int CAP, class SE>
@@ -625,13 +664,15 @@ PT_DEV bool MeshStep(const dscene& S, lane_state& L, tstack<SPILL, CAP, SE>& st)
     const unsigned long long mF = PtMaskNeU(L.nb, 0u);   // the wave's face lanes
     const bool face = PtLanes(mF);
     bool fmiss = true;
-    float fT, fU, fW, TA, TB;
-    uint32_t aw0, aw1, bw0, bw1, fVA, fVB;
+    float fT, TA, TB;
+    uint32_t aw0, aw1, bw0, bw1;
     uint32_t pair = L.na;
-    asm("" : "=v"(fT), "=v"(fU), "=v"(fW), "=v"(TA), "=v"(TB), "=v"(fVA), "=v"(fVB));
+    asm("" : "=v"(fT), "=v"(TA), "=v"(TB));
     asm("" : "=v"(aw0), "=v"(aw1), "=v"(bw0), "=v"(bw1));
     if (face) {
-        fmiss = FaceTest<sizeof(SE) == 2>(S, L.na, L, L.na < L.nb, fT, fU, fW, fVA, fVB);
+        float fU, fW;
+        uint32_t I0, I1, I2;   // not read: the vertex indices are MeshEnd's
+        fmiss = FaceTest<sizeof(SE) == 2>(S, L.na, L, L.na < L.nb, fT, fU, fW, I0, I1, I2);
     } else {
         float4 a0, a1, b0, b1;
         if (sizeof(SE) == 2) {
@@ -662,11 +703,7 @@ PT_DEV bool MeshStep(const dscene& S, lane_state& L, tstack<SPILL, CAP, SE>& st)
     const bool anyF = mF != 0, anyI = (PtActive() & ~mF) != 0;
     if (anyF) {
         L.Time = fmiss ? L.Time : fT;
-        L.Shape = fmiss ? L.Shape : 0xFFFFFFFEu;
         L.Prim = fmiss ? L.Prim : L.na;
-        L.HA = fmiss ? L.HA : fVA;
-        L.HB = fmiss ? L.HB : fVB;
-        L.C = v3(fmiss ? L.C.x : 1 - fU - fW, fmiss ? L.C.y : fU, fmiss ? L.C.z : fW);
     }
     // A face lane moves on to its leaf's next face; an internal lane takes
     // the reference's three-way decision (LaneStep).  The flags are the
